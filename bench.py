@@ -3,7 +3,7 @@
 of the 2D Laplace system -- BASELINE.json config C2: Solver2D, FCNN(2-32-32-1, tanh), DirichletBVP2D,
 Generator2D 256x256 = 65 536 noisy-grid points per batch per GPU, fp32 -- through ``Solver2D.run_train_epoch()``.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cX] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cX] [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver with torch.distributed.run (one rank per MI355X); scaling is WEAK by default: every rank
 trains on its own 65 536-point shard of a global N*65 536-point batch and joins one all-reduce of the flat
@@ -12,14 +12,21 @@ trains on its own 65 536-point shard of a global N*65 536-point batch and joins 
 kernel (forward streams + traced pointwise stage + reverse pass) and the second-stage sums / [exchange] / device-side
 epoch tail (loss history, best-network snapshot, fused Adam) -- and no host synchronisation.
 
-Timing: W untimed warm-up steps, then windows of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize()
-on both sides (max over ranks), repeated until >= 0.25 s and >= 3 windows have been timed; the MEDIAN window is reported.
-Inputs of the headline ``value`` are pre-sampled (reference RNG order) and resident in HBM before the timed region
-(``ResidentBatchGenerator``); the figure with host sampling + PCIe upload inside the step is reported separately as
-``with_host_sampling`` (like for like with the CPU baseline's full step), the one with a fresh batch drawn by the
-device-side Philox sampler every step as ``with_device_sampling``.
+Timing: W untimed warm-up steps, then ONE window of exactly K timed steps, bracketed by barrier + torch.cuda.synchronize()
+on both sides (max over ranks); ``ms_per_step`` = window / K.  Inputs of the headline ``value`` are pre-sampled (reference
+RNG order) and resident in HBM before the timed region (``ResidentBatchGenerator``).  ``--dump-outputs DIR`` then writes
+what the last timed step left for its caller -- every network parameter after the Adam update and that step's training
+loss -- as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for
+output.
 
-Rank 0 prints ONE JSON line (contract in the task description) including
+A plain run does only that and prints ONE JSON line (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step``, ...).  ``--full`` adds everything else, after the headline and on rank 0 of a single-process run unless
+said otherwise (``--no-cpu-baseline``, ``--no-configs``, ``--no-traffic``, ``--no-cold-start`` leave legs out):
+  headline_windowed -- the same step timed the earlier way: windows of K steps repeated until >= 0.25 s and >= 3 windows
+                   have been timed, the MEDIAN window (every rank, also with --config / --scaling),
+  with_host_sampling, with_device_sampling, default_generator_cuda -- the step with host sampling + PCIe upload inside it
+                   (like for like with the CPU baseline's full step), with a fresh batch drawn by the device-side Philox
+                   sampler every step, and under torch.set_default_device('cuda'),
   roofline      -- dominant kernel (fused closure kernel): algorithmic GEMM flops / HIP-event launch time vs the fp32
                    MFMA peak, plus the HBM bytes per launch MEASURED IN THIS RUN (two child runs of this script under
                    rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, outside the timed region; when rocprofv3 is missing the last
@@ -390,6 +397,50 @@ def timed_windows(step, k, barrier, reduce_max=None, min_total_s=0.25, max_windo
     return sorted(times)
 
 
+def timed_steps(step, k, barrier, reduce_max=None):
+    """Seconds taken by EXACTLY ``k`` steps in one window, bracketed by barrier + synchronize on both sides (max over ranks)."""
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(k):
+        step()
+    barrier()
+    dt = time.perf_counter() - t0
+    if reduce_max is not None:
+        dt = reduce_max([dt])[0]
+    return dt
+
+
+def windowed_record(step, k, barrier, reduce_max, points):
+    """``--full``: the step timed the way the headline used to be -- windows of ``k`` steps repeated until >= 0.25 s and
+    >= 3 windows have been timed, the median window (``timed_windows``)."""
+    w = timed_windows(step, k, barrier, reduce_max)
+    dt = w[(len(w) - 1) // 2]
+    return {"value": points / (dt / k), "ms_per_step": dt / k * 1e3, "windows": len(w), "steps_per_window": k,
+            "statistic": "median window", "window_ms_min": w[0] * 1e3, "window_ms_median": dt * 1e3,
+            "window_ms_max": w[-1] * 1e3, "timed_total_s": sum(w)}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, solver):
+    """``--dump-outputs DIR``: what the timed path hands its caller after its last step -- every parameter of every network
+    (the modules' own tensors, updated in place by the fused Adam step) and that step's training loss -- as DIR/<name>.npy
+    (``net<i>.<parameter name>.npy`` in the network's precision, ``train_loss.npy`` in float64).  Call after a synchronize."""
+    import numpy as np
+    arrays = {"train_loss": np.asarray([solver.metrics_history["train_loss"][-1]], dtype=np.float64)}
+    for i, net in enumerate(solver.nets):
+        for name, p in net.named_parameters():
+            a = p.detach().cpu().numpy()
+            arrays[f"net{i}.{name}"] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def config_record(name, size=None):
     """One other BASELINE config at its stated size through run_train_epoch() on resident pre-sampled batches:
     ms per step (median of >= 0.25 s of windows), points/s, algorithmic TFLOP/s and fraction of the fp32 MFMA peak."""
@@ -546,18 +597,24 @@ def scaling_run(args, world, rank, use_dist, dist):
         return t.tolist()
     for _ in range(args.warmup):
         solver.run_train_epoch()
-    windows = timed_windows(solver.run_train_epoch, args.steps, barrier, reduce_max if use_dist else None)
-    dt = windows[(len(windows) - 1) // 2]
+    dt = timed_steps(solver.run_train_epoch, args.steps, barrier, reduce_max if use_dist else None)
     per_rank = hi - lo
     total = per_rank * world
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver)
+    final_loss = solver.metrics_history["train_loss"][-1]
+    windowed = None
+    if args.full:
+        windowed = windowed_record(solver.run_train_epoch, args.steps, barrier, reduce_max if use_dist else None, total)
     if rank == 0:
         step_s = dt / args.steps
         tf = ALGO_FLOP_PER_PT[name] * total / step_s / 1e12
-        print(json.dumps({
+        out = {
             "metric": f"collocation-points/sec (residual+bwd), config {name.upper()}, {args.scaling} scaling",
             "value": total / step_s, "unit": "collocation-points/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": step_s * 1e3,
-            "timing": {"windows": len(windows), "steps_per_window": args.steps, "statistic": "median window"},
+            "timing": {"windows": 1, "steps_per_window": args.steps, "statistic": "one window of exactly --steps steps",
+                       "timed_total_s": dt},
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{name.upper()} of BASELINE.json at its stated size through run_train_epoch()",
                        "points_per_gpu": per_rank, "global_batch": total,
@@ -565,7 +622,10 @@ def scaling_run(args, world, rank, use_dist, dist):
                        "inputs": "pre-sampled in the reference's RNG order, resident in HBM"},
             "algorithmic_tflops": tf, "frac_of_fp32_mfma_peak_per_gpu": tf / world / FP32_MFMA_PEAK_TFLOPS,
             "single_launch": solver._fused_sys.fusedk is not None,
-            "final_loss": solver.metrics_history["train_loss"][-1]}), flush=True)
+            "final_loss": final_loss}
+        if windowed is not None:
+            out["headline_windowed"] = windowed
+        print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()
         solver.dist.close()
@@ -575,9 +635,15 @@ def scaling_run(args, world, rank, use_dist, dist):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    # defaults: windows of ~55 ms, repeated until >= 0.25 s (and >= 3 windows) have been timed; the median window counts
+    # exactly --steps timed steps in one window (--full: also windows of --steps steps repeated until >= 0.25 s)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (network parameters, training loss) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: windowed timing, roofline / per-kernel figures, other "
+                         "sampling routes, the other configs, fp64 legs, cold start, CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the per-config sub-records (C1, C3, C4, C5)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
@@ -647,9 +713,8 @@ def main():
         torch.cuda.synchronize()
 
     # W untimed warm-up steps (the closure kernel's first-use self-check, buffer allocation and the host path warm up
-    # here), then windows of EXACTLY K steps, each bracketed by barrier + synchronize; a window of the driver's K = 20
-    # is 0.5 ms, so windows are repeated until >= 0.25 s has been timed and the MEDIAN window is reported (an MI355X
-    # also needs tens of ms of sustained work to reach its clocks: the first windows of a cold box are slower).
+    # here; an MI355X also needs tens of ms of sustained work to reach its clocks), then ONE window of exactly K steps,
+    # bracketed by barrier + synchronize
     for _ in range(args.warmup):
         solver.run_train_epoch()
 
@@ -657,8 +722,7 @@ def main():
         t = torch.tensor(vals, dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return t.tolist()
-    windows = timed_windows(solver.run_train_epoch, args.steps, barrier, reduce_max if use_dist else None)
-    dt = windows[(len(windows) - 1) // 2]
+    dt = timed_steps(solver.run_train_epoch, args.steps, barrier, reduce_max if use_dist else None)
     assert solver.fused_active
     # the headline is the single-launch closure kernel: if its first-use self-check (engine.verify_fused) rejected it,
     # the numbers below would silently be the three-kernel pipeline's -- refuse instead
@@ -666,6 +730,15 @@ def main():
         f"single-launch closure kernel not in use: {getattr(solver._fused_sys, 'fused_check', None)}"
     ms = dt / args.steps * 1e3
     value = N_POINTS * world / (dt / args.steps)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver)
+    final_loss = solver.metrics_history["train_loss"][-1]
+    # --full: the same step by the earlier protocol -- windows of K steps repeated until >= 0.25 s, the MEDIAN window (a
+    # window of K = 20 is 0.5 ms; the first windows of a cold box are slower)
+    windowed = None
+    if args.full:
+        windowed = windowed_record(solver.run_train_epoch, args.steps, barrier, reduce_max if use_dist else None,
+                                   N_POINTS * world)
 
     out = None
     if rank == 0:
@@ -673,9 +746,8 @@ def main():
             "metric": "collocation-points/sec (residual+bwd), 2D Laplace 65k pts, 1/2/4/8 GPU",
             "value": value, "unit": "collocation-points/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms,
-            "timing": {"windows": len(windows), "steps_per_window": args.steps, "statistic": "median window",
-                       "window_ms_min": windows[0] * 1e3, "window_ms_median": dt * 1e3, "window_ms_max": windows[-1] * 1e3,
-                       "timed_total_s": sum(windows)}, "higher_is_better": True, "scaling": "weak",
+            "timing": {"windows": 1, "steps_per_window": args.steps, "statistic": "one window of exactly --steps steps",
+                       "timed_total_s": dt}, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "C2: Solver2D 2D Laplace, DirichletBVP2D, FCNN(2-32-32-1, tanh), Generator2D "
                                    "256x256 = 65536 noisy-grid points per GPU per step, Adam(1e-3), "
@@ -684,11 +756,13 @@ def main():
                        "parallelism": f"dp{world} (shard-by-batch, one all-reduce of [P+1] fp32 per step)",
                        "allreduce": ("none (single process)" if not use_dist else solver.dist.allreduce_kind("cuda")),
                        "inputs": "pre-sampled in the reference's RNG order, resident in HBM"},
-            "final_loss": solver.metrics_history["train_loss"][-1],
+            "final_loss": final_loss,
         }
+        if windowed is not None:
+            out["headline_windowed"] = windowed
         if use_dist and hasattr(solver.dist._direct, "status"):
             out["allreduce_flag_timeouts"] = solver.dist._direct.status()      # one-shot exchange: must be 0
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         # the same training epochs inside fit(): whole chunks of epochs per native call (ndq_fused_fit_run), no Python in
         # between -- at this size the step is GPU-bound either way; listed so that the two routes can be compared
         kf = max(args.steps, 200)
@@ -697,7 +771,7 @@ def main():
         dtf = tf_[(len(tf_) - 1) // 2] / kf
         out["in_fit"] = {"value": N_POINTS / dtf, "ms_per_step": dtf * 1e3, "epochs_per_call": kf,
                          "note": "fit(k) with n_batches_valid = 0: the headline's training epochs issued k per native call"}
-    if rank == 0 and world == 1 and not use_dist:
+    if args.full and rank == 0 and world == 1 and not use_dist:
         system = solver._fused_sys
         batch = solver._generate_batch("train")
         from neurodiffeq_amd.engine import FusedSystem

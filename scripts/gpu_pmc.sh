@@ -5,7 +5,7 @@
 # FETCH_SIZE / WRITE_SIZE can be read against a calibration from the same box and the same tool.
 TAG=${1:-pmc}; shift
 CMD=("$@")
-[ ${#CMD[@]} -eq 0 ] && CMD=(python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-configs)
+[ ${#CMD[@]} -eq 0 ] && CMD=(python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-configs)
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
