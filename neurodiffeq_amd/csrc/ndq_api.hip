@@ -69,12 +69,6 @@ namespace ndq {
 static const ndq_mlp_kernels kTable[] = {NDQ_CFG_TABLE(NDQ_ENTRY)};
 static std::vector<const ndq_mlp_kernels*> g_registered;     // extension modules (ndq_mlp_register)
 
-static bool same_desc(const ndq_mlp_desc& a, const ndq_mlp_desc& b) {
-  return a.d == b.d && a.first == b.first && a.mask2 == b.mask2 && a.hidden == b.hidden && a.layers == b.layers &&
-         a.act == b.act && a.n_out == b.n_out && a.lap == b.lap && a.skip == b.skip && a.mask3 == b.mask3 && a.mask4 == b.mask4 &&
-         a.actp == b.actp && a.widths == b.widths && a.mono == b.mono;
-}
-
 static const ndq_mlp_kernels* find(const ndq_mlp_desc* d) {
   if (!d || d->hidden < 1 || d->hidden > NDQ_MAX_HIDDEN) return nullptr;
   for (const ndq_mlp_kernels& e : kTable)
@@ -82,14 +76,6 @@ static const ndq_mlp_kernels* find(const ndq_mlp_desc* d) {
   for (const ndq_mlp_kernels* e : g_registered)
     if (same_desc(e->desc, *d)) return e;
   return nullptr;
-}
-
-static int bwd_blocks(const ndq_mlp_kernels* e, int n) {
-  const int tiles = (n + 15) / 16;
-  int blocks = (tiles + e->bwd_waves - 1) / e->bwd_waves;
-  if (blocks > NDQ_BWD_MAX_BLOCKS) blocks = NDQ_BWD_MAX_BLOCKS;
-  if (blocks < 1) blocks = 1;
-  return blocks;
 }
 
 // ---------------------------------------------------------------------------------------------- reduction
@@ -218,38 +204,8 @@ __global__ __launch_bounds__(1024) void reduce_grad_loss_kernel(Reduce2Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------- epoch tail
-struct TailArgs {
-  float* p; const float* g; float* m; float* v; int len;
-  float lr, b1, b2, eps, wd, bc1, bc2s;
-  // where the parameters / moments this epoch started from live, when that is not p / m / v (fit() in pull mode keeps
-  // two sets of buffers; the tail that closes a call brings the result home): nullptr = in place
-  const float* p_in; const float* m_in; const float* v_in;
-  const float* loss_slots; int nb; float* loss_hist; int hist_index; float* best_loss; int parity; float* best_flat;
-  int write_scalars;
-};
-__global__ __launch_bounds__(256) void epoch_tail_kernel(TailArgs a) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  float loss = 0.f;
-  for (int k = 0; k < a.nb; ++k) loss += a.loss_slots[k];
-  loss /= (float)a.nb;
-  const float best = a.best_loss[a.parity];
-  const bool better = (a.best_flat != nullptr) && (loss < best);   // false for NaN, like the reference's comparison
-  if (i < a.len) {
-    const float pi = a.p[i];
-    if (better) a.best_flat[i] = pi;
-    if (a.m != nullptr) {             // validation epochs pass no optimiser state: bookkeeping only
-      float pn, mi, vi;
-      ndq::adam_value(ndq::AdamConsts{a.lr, a.b1, a.b2, a.eps, a.wd, a.bc1, a.bc2s}, pi, a.g[i], a.m[i], a.v[i], pn, mi, vi);
-      a.m[i] = mi;
-      a.v[i] = vi;
-      a.p[i] = pn;
-    }
-  }
-  if (i == 0 && a.write_scalars) {
-    a.loss_hist[a.hist_index] = loss;
-    a.best_loss[a.parity ^ 1] = better ? loss : best;
-  }
-}
+// (epoch_tail_kernel, the tail of an epoch whose sums are done already -- ndq_epoch_tail -- lives in ndq_tail.h: it is shared with libndq64.so)
+using TailArgs = ndq::TailArgsT<float>;
 
 // second-stage sums AND the epoch tail in one launch (single batch per epoch, no all-reduce in between): every
 // workgroup first adds up the loss partials itself (nlparts <= a few hundred floats), then reduces its 64 gradient
@@ -337,7 +293,7 @@ __device__ __forceinline__ void reduce_tail_body(const ReduceTailArgs& a) {
       for (int k = 0; k < 16; ++k) g += sm[k * TC + c];
       a.r.out[i] = g;
       float pn, mi, vi;
-      ndq::adam_value(ndq::AdamConsts{a.t.lr, a.t.b1, a.t.b2, a.t.eps, a.t.wd, a.t.bc1, a.t.bc2s}, pi, g, m0, v0, pn, mi, vi);
+      ndq::adam_value(a.t.adam, pi, g, m0, v0, pn, mi, vi);
       a.t.m[i] = mi;
       a.t.v[i] = vi;
       a.t.p[i] = pn;
@@ -438,7 +394,7 @@ __global__ __launch_bounds__(1024) void reduce_tail_dp_kernel(ReduceTailArgs a, 
     a.r.out[i] = g;
     if (better) a.t.best_flat[i] = pi;
     float pn, mi, vi;
-    ndq::adam_value(ndq::AdamConsts{a.t.lr, a.t.b1, a.t.b2, a.t.eps, a.t.wd, a.t.bc1, a.t.bc2s}, pi, g, m0, v0, pn, mi, vi);
+    ndq::adam_value(a.t.adam, pi, g, m0, v0, pn, mi, vi);
     a.t.m[i] = mi;
     a.t.v[i] = vi;
     a.t.p[i] = pn;
@@ -461,27 +417,15 @@ __global__ __launch_bounds__(TC * 16) void reduce_tail_multi_kernel(ReduceTailMu
   reduce_tail_body<TC>(mine);
 }
 // the sums / tail launch of all networks of a system: narrow workgroups where every loss partial has a thread of its own
-static void launch_tail_multi(const ReduceTailMultiArgs& a, int max_params, int n_nets, int max_lparts, hipStream_t st) {
+static int launch_tail_multi(ReduceTailMultiArgs& a, int max_params, int n_nets, int max_lparts, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  for (int k = n_nets; k < 4; ++k) a.net[k] = a.net[0];
   if (NDQ_TAIL_COLS < 64 && max_lparts <= NDQ_TAIL_COLS * 16)
     hipLaunchKernelGGL(reduce_tail_multi_kernel<NDQ_TAIL_COLS>, dim3((max_params + NDQ_TAIL_COLS - 1) / NDQ_TAIL_COLS, n_nets),
                        dim3(NDQ_TAIL_COLS * 16), 0, st, a);
   else
     hipLaunchKernelGGL(reduce_tail_multi_kernel<64>, dim3((max_params + 63) / 64, n_nets), dim3(1024), 0, st, a);
-}
-
-// ---------------------------------------------------------------------------------------------- Adam
-// torch.optim.Adam (amsgrad=False, maximize=False) single-tensor formula:
-//   g += wd*p; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, int len, float lr,
-                                                   float b1, float b2, float eps, float wd, float bc1, float bc2s) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= len) return;
-  float pn, mi, vi;
-  ndq::adam_value(ndq::AdamConsts{lr, b1, b2, eps, wd, bc1, bc2s}, p[i], g[i], m[i], v[i], pn, mi, vi);
-  m[i] = mi;
-  v[i] = vi;
-  p[i] = pn;
+  return (int)hipGetLastError();
 }
 
 }  // namespace ndq
@@ -514,7 +458,7 @@ int ndq_mlp_bwd_blocks(const ndq_mlp_desc* desc, int n) {
   const ndq_mlp_kernels* e = find(desc);
   if (!e) return NDQ_EUNSUPPORTED;
   if (n <= 0) return NDQ_EINVAL;
-  return bwd_blocks(e, n);
+  return bwd_blocks(e->bwd_waves, n);
 }
 
 int ndq_mlp_jet_fwd(const ndq_mlp_desc* desc, const float* coords, int ldc, int n, const float* params, float* jets,
@@ -530,7 +474,7 @@ int ndq_mlp_jet_bwd(const ndq_mlp_desc* desc, const float* coords, int ldc, int 
   const ndq_mlp_kernels* e = find(desc);
   if (!e) return NDQ_EUNSUPPORTED;
   if (!coords || !params || !gbar || !partials || n <= 0 || ldc < n || ldj < n) return NDQ_EINVAL;
-  return e->bwd(coords, ldc, n, params, gbar, ldj, partials, bwd_blocks(e, n), stream);
+  return e->bwd(coords, ldc, n, params, gbar, ldj, partials, bwd_blocks(e->bwd_waves, n), stream);
 }
 
 int ndq_reduce_partials(const float* partials, int nparts, int len, float* out, int accumulate, float scale,
@@ -559,18 +503,38 @@ int ndq_epoch_tail(float* params, const float* grad, float* exp_avg, float* exp_
     return NDQ_EINVAL;
   TailArgs a{};
   a.p = params; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.len = len;
-  a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay;
-  a.bc1 = adam ? (float)(1.0 - pow((double)beta1, (double)step)) : 1.f;
-  a.bc2s = adam ? (float)sqrt(1.0 - pow((double)beta2, (double)step)) : 1.f;
+  a.adam = adam_consts(lr, beta1, beta2, eps, weight_decay, adam ? step : 0);
   a.loss_slots = loss_slots; a.nb = n_batches; a.loss_hist = loss_hist; a.hist_index = hist_index;
   a.best_loss = best_loss; a.parity = parity; a.best_flat = best_flat; a.write_scalars = write_scalars;
-  hipLaunchKernelGGL(epoch_tail_kernel, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(epoch_tail_kernel<float>, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
 }
 
-static void fill_reduce_tail(ReduceTailArgs& a, const ndq_fused_step* s, const float* loss_partials, int blocks, float seed,
-                             float* loss_hist, float* best_loss, int adam_step, int hist_index, int parity,
-                             int write_scalars);
+}  // extern "C"
+
+// The arguments of ONE sums + tail launch for network `s` -- every route (single GPU, data parallel, multi-network,
+// fit() in its three modes) builds them here.  `s0`: the network whose seed / loss_hist / best_loss count (net[0] of a
+// system).  part / lpart: the gradient and loss partial rows, nparts of each; nparts = 0: no training part (no sums, no
+// Adam: a validation tail).  adam_step <= 0: no optimiser step.  best_flat: where to snapshot the pre-update parameters
+// when the tracked loss improved (nullptr: this launch only hands the best value on).  v: the validation loss this launch
+// records, if any.  p_in / m_in / v_in: the state the epoch started from when that is not s.params / adam_m / adam_v.
+static ReduceTailArgs reduce_tail_args(const ndq_fused_step& s, const ndq_fused_step& s0, const float* part, const float* lpart,
+                                       int nparts, int adam_step, int hist_index, int parity, int write_scalars,
+                                       float* best_flat, const ValidArgs& v = ValidArgs{}, const float* p_in = nullptr,
+                                       const float* m_in = nullptr, const float* v_in = nullptr) {
+  ReduceTailArgs a{};
+  a.r = Reduce2Args{part, nparts, s.n_params, s.grad, 0, lpart, nparts, s.loss_slot, s0.seed};
+  a.t.p = s.params; a.t.g = s.grad; a.t.m = s.adam_m; a.t.v = s.adam_v; a.t.len = s.n_params;
+  a.t.adam = adam_consts(s.lr, s.beta1, s.beta2, s.eps, s.weight_decay, adam_step);
+  a.t.p_in = p_in; a.t.m_in = m_in; a.t.v_in = v_in;
+  a.t.loss_slots = s.loss_slot; a.t.nb = 1; a.t.loss_hist = s0.loss_hist; a.t.hist_index = hist_index;
+  a.t.best_loss = s0.best_loss; a.t.parity = parity; a.t.best_flat = best_flat; a.t.write_scalars = write_scalars;
+  a.tail_blocks = 0x7fffffff;
+  a.v = v;
+  return a;
+}
+
+extern "C" {
 
 int ndq_fused_step_run(const ndq_fused_step* s, const float* coords, int adam_step, int hist_index, int parity,
                        void* stream) {
@@ -582,19 +546,10 @@ int ndq_fused_step_run(const ndq_fused_step* s, const float* coords, int adam_st
     return ndq_reduce_grad_loss(s->partials, s->blocks, s->n_params, s->grad, 0, s->loss_partials, s->blocks,
                                 s->loss_slot, s->seed, stream);
   if (adam_step <= 0 || hist_index < 0 || (parity != 0 && parity != 1) || !s->loss_hist || !s->best_loss) return NDQ_EINVAL;
-  if (s->allreduce == reinterpret_cast<ndq_allreduce_fn>(&ndq_oneshot_allreduce) && s->comm &&
-      ((s->n_params + 63) / 64) * 65 <= static_cast<ndq::Oneshot*>(s->comm)->dev.max_len &&
-      (s->n_params + 63) / 64 <= static_cast<ndq::Oneshot*>(s->comm)->dev.max_blocks) {
-    // data parallel over the one-shot exchange: local sums + exchange + tail in ONE launch (reduce_tail_dp_kernel)
-    ndq::Oneshot* c = static_cast<ndq::Oneshot*>(s->comm);
-    ReduceTailArgs a{};
-    fill_reduce_tail(a, s, s->loss_partials, s->blocks, s->seed, s->loss_hist, s->best_loss, adam_step, hist_index, parity, 1);
-    const unsigned step = ++c->step;
-    hipLaunchKernelGGL(reduce_tail_dp_kernel, dim3((s->n_params + 63) / 64), dim3(1024), 0, static_cast<hipStream_t>(stream), a,
-                       c->dev, step);
-    return (int)hipGetLastError();
-  }
-  if (s->allreduce) {
+  const bool oneshot = s->allreduce == reinterpret_cast<ndq_allreduce_fn>(&ndq_oneshot_allreduce) && s->comm &&
+                       ((s->n_params + 63) / 64) * 65 <= static_cast<ndq::Oneshot*>(s->comm)->dev.max_len &&
+                       (s->n_params + 63) / 64 <= static_cast<ndq::Oneshot*>(s->comm)->dev.max_blocks;
+  if (s->allreduce && !oneshot) {
     // data parallel: local second-stage sums -> ONE all-reduce of [grad | loss] -> tail on the reduced vector
     if (s->loss_slot != s->grad + s->n_params) return NDQ_EINVAL;
     rc = ndq_reduce_grad_loss(s->partials, s->blocks, s->n_params, s->grad, 0, s->loss_partials, s->blocks, s->loss_slot,
@@ -606,16 +561,17 @@ int ndq_fused_step_run(const ndq_fused_step* s, const float* coords, int adam_st
                           s->weight_decay, adam_step, s->loss_slot, 1, s->loss_hist, hist_index, s->best_loss, parity,
                           s->best_flat, 1, stream);
   }
-  ReduceTailArgs a{};
-  a.r = Reduce2Args{s->partials, s->blocks, s->n_params, s->grad, 0, s->loss_partials, s->blocks, s->loss_slot, s->seed};
-  a.t.p = s->params; a.t.g = s->grad; a.t.m = s->adam_m; a.t.v = s->adam_v; a.t.len = s->n_params;
-  a.t.lr = s->lr; a.t.b1 = s->beta1; a.t.b2 = s->beta2; a.t.eps = s->eps; a.t.wd = s->weight_decay;
-  a.t.bc1 = (float)(1.0 - pow((double)s->beta1, (double)adam_step));
-  a.t.bc2s = (float)sqrt(1.0 - pow((double)s->beta2, (double)adam_step));
-  a.t.loss_slots = s->loss_slot; a.t.nb = 1; a.t.loss_hist = s->loss_hist; a.t.hist_index = hist_index;
-  a.t.best_loss = s->best_loss; a.t.parity = parity; a.t.best_flat = s->best_flat; a.t.write_scalars = 1;
-  a.tail_blocks = (s->n_params + 63) / 64;
-  int blocks = a.tail_blocks;
+  ReduceTailArgs a = reduce_tail_args(*s, *s, s->partials, s->loss_partials, s->blocks, adam_step, hist_index, parity, 1,
+                                      s->best_flat);
+  int blocks = (s->n_params + 63) / 64;
+  if (oneshot) {
+    // data parallel over the one-shot exchange: local sums + exchange + tail in ONE launch (reduce_tail_dp_kernel)
+    ndq::Oneshot* c = static_cast<ndq::Oneshot*>(s->comm);
+    const unsigned step = ++c->step;
+    hipLaunchKernelGGL(reduce_tail_dp_kernel, dim3(blocks), dim3(1024), 0, static_cast<hipStream_t>(stream), a, c->dev, step);
+    return (int)hipGetLastError();
+  }
+  a.tail_blocks = blocks;
   if (s->next_sampler) {
     rc = ndq::fill_sample_args(a.smp, s->next_sampler, s->next_seed, s->next_draw, s->next_stream, s->next_coords,
                                s->next_ldc);
@@ -624,20 +580,6 @@ int ndq_fused_step_run(const ndq_fused_step* s, const float* coords, int adam_st
   }
   hipLaunchKernelGGL(reduce_tail_kernel, dim3(blocks), dim3(1024), 0, static_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
-}
-
-static void fill_reduce_tail(ReduceTailArgs& a, const ndq_fused_step* s, const float* loss_partials, int blocks, float seed,
-                             float* loss_hist, float* best_loss, int adam_step, int hist_index, int parity,
-                             int write_scalars) {
-  a.r = Reduce2Args{s->partials, blocks, s->n_params, s->grad, 0, loss_partials, blocks, s->loss_slot, seed};
-  a.t.p = s->params; a.t.g = s->grad; a.t.m = s->adam_m; a.t.v = s->adam_v; a.t.len = s->n_params;
-  a.t.lr = s->lr; a.t.b1 = s->beta1; a.t.b2 = s->beta2; a.t.eps = s->eps; a.t.wd = s->weight_decay;
-  a.t.bc1 = (float)(1.0 - pow((double)s->beta1, (double)adam_step));
-  a.t.bc2s = (float)sqrt(1.0 - pow((double)s->beta2, (double)adam_step));
-  a.t.loss_slots = s->loss_slot; a.t.nb = 1; a.t.loss_hist = loss_hist; a.t.hist_index = hist_index;
-  a.t.best_loss = best_loss; a.t.parity = parity; a.t.best_flat = s->best_flat; a.t.write_scalars = write_scalars;
-  a.tail_blocks = 0x7fffffff;
-  a.v = ValidArgs{};
 }
 
 int ndq_fused_multi_step_run(const ndq_fused_step* steps, int n_nets, ndq_fused_launch_multi_fn launch,
@@ -661,17 +603,172 @@ int ndq_fused_multi_step_run(const ndq_fused_step* steps, int n_nets, ndq_fused_
   ReduceTailMultiArgs a{};
   int max_params = 0;
   for (int k = 0; k < n_nets; ++k) {
-    fill_reduce_tail(a.net[k], &steps[k], s0.loss_partials, s0.blocks, s0.seed, s0.loss_hist, s0.best_loss, adam_step,
-                     hist_index, parity, k == 0 ? 1 : 0);
+    a.net[k] = reduce_tail_args(steps[k], s0, steps[k].partials, s0.loss_partials, s0.blocks, adam_step, hist_index, parity,
+                                k == 0 ? 1 : 0, steps[k].best_flat);
     if (steps[k].n_params > max_params) max_params = steps[k].n_params;
   }
-  for (int k = n_nets; k < 4; ++k) a.net[k] = a.net[0];
-  launch_tail_multi(a, max_params, n_nets, s0.blocks, static_cast<hipStream_t>(stream));
-  return (int)hipGetLastError();
+  return launch_tail_multi(a, max_params, n_nets, s0.blocks, stream);
 }
 
-// ndq_fused_fit_run: see include/ndq.h.  Per epoch ONE closure launch (training workgroups + validation workgroups) and
-// ONE sums / tail launch (blockIdx.y = network); a trailing validation-only pair closes the call.
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- fit()
+// ndq_fused_fit_run: see include/ndq.h.  One validated call, shared by its three routes.  Buffer set 0 is the primary
+// state (net[k].params / adam_m / adam_v / partials, loss partials), set 1 the alt_* members pull and loop mode need.
+struct FitCall {
+  const ndq_fused_fit* f;
+  int n_epochs; const float* const* train_coords;
+  int adam_step, hist_index, valid_index;        // of the call's first epoch
+  void* stream;
+  bool valid;
+  int max_params, max_lparts;
+  float* P[2][4]; float* M[2][4]; float* V[2][4]; float* PART[2][4]; float* LP[2]; float* VP[2];
+};
+
+// What the snapshot of a launch follows: the training loss (track_best = 1) or the validation loss (2).  A launch that does
+// not carry that loss only hands the best value on to the other slot of the ping-pong.
+static bool fit_tracks(const ndq_fused_fit* f, bool with_train, bool with_valid) {
+  return (f->track_best == 1 && with_train) || (f->track_best == 2 && with_valid);
+}
+
+// Sums + tail launch of all networks, reading buffer set `set`: the training epoch with Adam step `adam_step` (with_train)
+// and / or the validation loss -> valid_hist[vindex] (with_valid); set != 0 also brings parameters and moments home.
+static int fit_tail(const FitCall& c, int set, bool with_train, bool with_valid, int adam_step, int hist_index, int vindex,
+                    int parity) {
+  const ndq_fused_fit* f = c.f;
+  const ndq_fused_step& s0 = f->net[0];
+  ValidArgs v{};
+  if (with_valid) v = ValidArgs{c.VP[set], f->valid_blocks, f->valid_scale, f->valid_hist, vindex, f->track_best == 2 ? 1 : 0};
+  const bool track = fit_tracks(f, with_train, with_valid);
+  ReduceTailMultiArgs a{};
+  for (int k = 0; k < f->n_nets; ++k) {
+    const ndq_fused_step& s = f->net[k];
+    a.net[k] = reduce_tail_args(s, s0, c.PART[set][k], c.LP[set], with_train ? s0.blocks : 0, with_train ? adam_step : 0,
+                                hist_index, parity, k == 0 ? 1 : 0, track ? s.best_flat : nullptr, v,
+                                set ? c.P[set][k] : nullptr, set ? c.M[set][k] : nullptr, set ? c.V[set][k] : nullptr);
+  }
+  return launch_tail_multi(a, c.max_params, f->n_nets, c.max_lparts, c.stream);
+}
+
+// Per epoch ONE closure launch (training workgroups + validation workgroups) and ONE sums / tail launch (blockIdx.y =
+// network); a trailing validation-only pair closes the call.  Tail e < n_epochs: training epoch e + the validation loss
+// of epoch e - 1.
+static int fit_two_launch(const FitCall& c, int parity) {
+  const ndq_fused_fit* f = c.f;
+  const ndq_fused_step& s0 = f->net[0];
+  for (int e = 0; e < c.n_epochs; ++e, parity ^= 1) {
+    if (!c.train_coords[e]) return NDQ_EINVAL;
+    const bool with_valid = c.valid && e > 0;
+    int rc = f->launch(c.train_coords[e], s0.ldc, s0.n, c.P[0], c.PART[0], c.LP[0], s0.seed,
+                       with_valid ? f->valid_coords : nullptr, f->valid_ldc, with_valid ? f->valid_n : 0, c.VP[0], nullptr,
+                       c.stream);
+    if (rc) return rc;
+    rc = fit_tail(c, 0, true, with_valid, c.adam_step + e, c.hist_index + e, c.valid_index + e - 1, parity);
+    if (rc) return rc;
+  }
+  if (!c.valid) return 0;
+  int rc = f->launch(nullptr, 0, 0, c.P[0], nullptr, nullptr, 0.f, f->valid_coords, f->valid_ldc, f->valid_n, c.VP[0], nullptr,
+                     c.stream);
+  if (rc) return rc;
+  return fit_tail(c, 0, false, true, 0, c.hist_index + c.n_epochs, c.valid_index + (c.n_epochs > 0 ? c.n_epochs - 1 : 0), parity);
+}
+
+// ---- pull and loop mode: launch e = 0 .. last of the sequence runs the training closure of epoch e (e < n_epochs), the
+// validation closure on the parameters it starts from (valid && e >= 1), and FIRST, in its prologue (e >= 1), finishes
+// training epoch e - 1 from buffer set (e - 1) & 1 into set e & 1.  What launch e finishes -- the ONE definition for the
+// host of pull mode, the bias corrections of loop mode (whose device code, ndq_tail.h loop_pull_args, counts the same way)
+// and the tail that closes the call, which is launch last + 1 without closures:
+struct Finishes { int adam_step, hist_index, valid_index; bool with_valid; };
+static Finishes launch_finishes(const FitCall& c, int e) {
+  const int j = e - 1;                            // the training epoch; its launch also evaluated the validation of epoch j - 1
+  return {c.adam_step + j, c.hist_index + j, c.valid_index + j - 1, c.valid && j >= 1};
+}
+static int fit_last_launch(const FitCall& c) { return c.valid ? c.n_epochs : c.n_epochs - 1; }
+
+// the call's last launch: an ordinary tail, reading set `fin`, that leaves everything in the primary buffers -- with a
+// validation batch the validation of the last epoch (no Adam), else the last training epoch's update
+static int fit_closing_tail(const FitCall& c, int fin, int parity) {
+  const Finishes w = launch_finishes(c, fit_last_launch(c) + 1);
+  return fit_tail(c, fin, !c.valid, c.valid, w.adam_step, w.hist_index, w.valid_index, parity);
+}
+
+// PULL MODE: one launch per epoch
+static int fit_pull(const FitCall& c, int parity) {
+  const ndq_fused_fit* f = c.f;
+  const ndq_fused_step& s0 = f->net[0];
+  const int last = fit_last_launch(c);
+  for (int e = 0; e <= last; ++e) {
+    ndq::PullArgs pa{};
+    if (e >= 1) {
+      const Finishes w = launch_finishes(c, e);
+      const int in = (e - 1) & 1, out = e & 1;
+      pa.enabled = 1; pa.n_nets = f->n_nets; pa.nparts = s0.blocks;
+      pa.lpart = c.LP[in]; pa.nlparts = s0.blocks; pa.lscale = s0.seed;
+      pa.loss_hist = s0.loss_hist; pa.hist_index = w.hist_index; pa.loss_slot = s0.loss_slot;
+      pa.vpart = w.with_valid ? c.VP[in] : nullptr; pa.nvparts = f->valid_blocks; pa.vscale = f->valid_scale;
+      pa.valid_hist = f->valid_hist; pa.valid_index = w.valid_index; pa.best_on_valid = f->track_best == 2 ? 1 : 0;
+      pa.best_loss = s0.best_loss; pa.parity = parity;
+      const bool track = fit_tracks(f, true, w.with_valid);
+      for (int k = 0; k < f->n_nets; ++k) {
+        const ndq_fused_step& s = f->net[k];
+        ndq::PullNet& n = pa.net[k];
+        n.part = c.PART[in][k];
+        n.p_in = c.P[in][k]; n.m_in = c.M[in][k]; n.v_in = c.V[in][k];
+        n.p_out = c.P[out][k]; n.m_out = c.M[out][k]; n.v_out = c.V[out][k];
+        n.grad = s.grad; n.best_flat = track ? s.best_flat : nullptr; n.len = s.n_params;
+        n.adam = adam_consts(s.lr, s.beta1, s.beta2, s.eps, s.weight_decay, w.adam_step);
+      }
+      parity ^= 1;                                 // every prologue is a tail
+    }
+    const bool train_part = e < c.n_epochs, valid_part = c.valid && e >= 1;
+    if (train_part && !c.train_coords[e]) return NDQ_EINVAL;
+    int rc = f->launch(train_part ? c.train_coords[e] : nullptr, s0.ldc, train_part ? s0.n : 0, c.P[e & 1],
+                       train_part ? c.PART[e & 1] : nullptr, c.LP[e & 1], s0.seed, valid_part ? f->valid_coords : nullptr,
+                       f->valid_ldc, valid_part ? f->valid_n : 0, c.VP[e & 1], &pa, c.stream);
+    if (rc) return rc;
+  }
+  return fit_closing_tail(c, last & 1, parity);
+}
+
+// LOOP MODE: training and validation grid are ONE workgroup each -> runs of up to kLoopMaxLaunches launches of fit_pull's
+// sequence become one launch of one workgroup that keeps the state in LDS (csrc/ndq_tail.h: LoopArgs); segment i reads
+// buffer set i & 1 and leaves the other one.  `stride`: floats between the training batches of consecutive epochs.
+static int fit_loop(const FitCall& c, long long stride, int parity) {
+  const ndq_fused_fit* f = c.f;
+  const ndq_fused_step& s0 = f->net[0];
+  const int last = fit_last_launch(c);
+  int in = 0;
+  for (int e0 = 0; e0 <= last; e0 += ndq::kLoopMaxLaunches, in ^= 1) {
+    const int e1 = e0 + ndq::kLoopMaxLaunches <= last + 1 ? e0 + ndq::kLoopMaxLaunches : last + 1;
+    const int out = in ^ 1;
+    ndq::LoopArgs L{};
+    L.e0 = e0; L.e1 = e1; L.n_epochs = c.n_epochs; L.has_valid = c.valid ? 1 : 0; L.track_best = f->track_best;
+    L.hist_index = c.hist_index; L.valid_index = c.valid_index; L.parity = parity; L.coord_stride = stride;
+    L.lp_in = c.LP[in]; L.vp_in = c.VP[in]; L.lp_out = c.LP[out]; L.vp_out = c.VP[out];
+    L.lscale = s0.seed; L.vscale = f->valid_scale;
+    L.loss_hist = s0.loss_hist; L.loss_slot = s0.loss_slot; L.valid_hist = f->valid_hist; L.best_loss = s0.best_loss;
+    for (int k = 0; k < f->n_nets; ++k) {
+      const ndq_fused_step& s = f->net[k];
+      ndq::LoopNet& n = L.net[k];
+      n.p_in = c.P[in][k]; n.m_in = c.M[in][k]; n.v_in = c.V[in][k]; n.part_in = c.PART[in][k];
+      n.p_out = c.P[out][k]; n.m_out = c.M[out][k]; n.v_out = c.V[out][k]; n.part_out = c.PART[out][k];
+      n.grad = s.grad; n.best_flat = s.best_flat;
+      n.lr = s.lr; n.b1 = s.beta1; n.b2 = s.beta2; n.eps = s.eps; n.wd = s.weight_decay;
+      for (int e = e0 > 1 ? e0 : 1; e < e1; ++e) {
+        const ndq::AdamConsts a = adam_consts(s.lr, s.beta1, s.beta2, s.eps, s.weight_decay, launch_finishes(c, e).adam_step);
+        n.bc1[e - e0] = a.bc1; n.bc2s[e - e0] = a.bc2s;
+      }
+    }
+    int rc = f->launch_loop(c.train_coords[0], s0.ldc, s0.n, s0.seed, c.valid ? f->valid_coords : nullptr, f->valid_ldc,
+                            c.valid ? f->valid_n : 0, &L, c.stream);
+    if (rc) return rc;
+  }
+  // L.parity is the parity of the call's first launch in every segment (the kernel flips it per prologue): `last` prologues
+  return fit_closing_tail(c, in, parity ^ (last & 1));
+}
+
+extern "C" {
+
 int ndq_fused_fit_run(const ndq_fused_fit* f, int n_epochs, const float* const* train_coords, int adam_step,
                       int hist_index, int valid_index, int parity, void* stream) {
   if (!f || !f->launch || f->n_nets < 1 || f->n_nets > 4 || n_epochs < 0 || (n_epochs > 0 && (!train_coords || adam_step <= 0)) ||
@@ -683,200 +780,41 @@ int ndq_fused_fit_run(const ndq_fused_fit* f, int n_epochs, const float* const* 
   if (!s0.best_loss || (n_epochs > 0 && (!s0.loss_hist || !s0.loss_partials || s0.n <= 0 || s0.blocks <= 0))) return NDQ_EINVAL;
   if (valid && (!f->valid_loss_partials || !f->valid_hist || f->valid_n <= 0 || f->valid_blocks <= 0)) return NDQ_EINVAL;
   if (f->track_best == 2 && !valid) return NDQ_EINVAL;
-  const float* params[4];
-  float* partials[4];
-  int max_params = 0;
+  FitCall c{f, n_epochs, train_coords, adam_step, hist_index, valid_index, stream, valid};
+  c.max_lparts = s0.blocks > f->valid_blocks ? s0.blocks : f->valid_blocks;
+  c.LP[0] = s0.loss_partials; c.LP[1] = f->alt_loss_partials;
+  c.VP[0] = f->valid_loss_partials; c.VP[1] = f->alt_valid_loss_partials;
+  bool pull = f->pull_ok != 0 && n_epochs >= 2 && s0.blocks * f->n_nets <= ndq::kPullMaxWork && f->alt_loss_partials &&
+              (!valid || f->alt_valid_loss_partials);
   for (int k = 0; k < f->n_nets; ++k) {
     const ndq_fused_step& s = f->net[k];
     if (!s.params || s.n_params <= 0 || (f->track_best && !s.best_flat)) return NDQ_EINVAL;
     if (n_epochs > 0 && (!s.partials || !s.grad || !s.adam_m || !s.adam_v || !s.loss_slot)) return NDQ_EINVAL;
-    params[k] = s.params;
-    partials[k] = s.partials;
-    if (s.n_params > max_params) max_params = s.n_params;
+    if (s.n_params > c.max_params) c.max_params = s.n_params;
+    c.P[0][k] = s.params; c.M[0][k] = s.adam_m; c.V[0][k] = s.adam_v; c.PART[0][k] = s.partials;
+    c.P[1][k] = f->alt_params[k]; c.M[1][k] = f->alt_m[k]; c.V[1][k] = f->alt_v[k]; c.PART[1][k] = f->alt_partials[k];
+    pull = pull && c.P[1][k] && c.M[1][k] && c.V[1][k] && c.PART[1][k];
   }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int max_lparts = s0.blocks > f->valid_blocks ? s0.blocks : f->valid_blocks;
-  // tail of one epoch: e < n_epochs: training epoch e (+ the validation loss of epoch e - 1 if with_valid);
-  // e == n_epochs: the trailing validation epoch alone
-  auto tail = [&](int e, bool with_train, bool with_valid, int vindex) {
-    ReduceTailMultiArgs a{};
-    for (int k = 0; k < f->n_nets; ++k) {
-      const ndq_fused_step& s = f->net[k];
-      ReduceTailArgs& t = a.net[k];
-      t.r = Reduce2Args{s.partials, with_train ? s0.blocks : 0, s.n_params, s.grad, 0, s0.loss_partials,
-                        with_train ? s0.blocks : 0, s.loss_slot, s0.seed};
-      t.t.p = s.params; t.t.g = s.grad; t.t.m = s.adam_m; t.t.v = s.adam_v; t.t.len = s.n_params;
-      t.t.lr = s.lr; t.t.b1 = s.beta1; t.t.b2 = s.beta2; t.t.eps = s.eps; t.t.wd = s.weight_decay;
-      const int step = adam_step + e;
-      t.t.bc1 = with_train ? (float)(1.0 - pow((double)s.beta1, (double)step)) : 1.f;
-      t.t.bc2s = with_train ? (float)sqrt(1.0 - pow((double)s.beta2, (double)step)) : 1.f;
-      t.t.loss_slots = s.loss_slot; t.t.nb = 1; t.t.loss_hist = s0.loss_hist; t.t.hist_index = hist_index + e;
-      t.t.best_loss = s0.best_loss; t.t.parity = parity; t.t.write_scalars = (k == 0) ? 1 : 0;
-      // the snapshot follows the training loss (track_best = 1) or the validation loss (2): a tail that does not carry
-      // that loss only hands the best value on to the other slot of the ping-pong
-      const bool track = (f->track_best == 1 && with_train) || (f->track_best == 2 && with_valid);
-      t.t.best_flat = track ? s.best_flat : nullptr;
-      t.tail_blocks = 0x7fffffff;
-      if (with_valid)
-        t.v = ValidArgs{f->valid_loss_partials, f->valid_blocks, f->valid_scale, f->valid_hist, vindex, f->track_best == 2 ? 1 : 0};
+  if (!pull) return fit_two_launch(c, parity);
+  bool loop = f->loop_ok != 0 && f->launch_loop && s0.blocks == 1 && (!valid || f->valid_blocks == 1) &&
+              f->n_nets <= ndq::kLoopMaxNets;
+  long long stride = 0;
+  if (loop) {                  // ... and the batches of the epochs are equally spaced in memory
+    if (!train_coords[0] || !train_coords[1]) return NDQ_EINVAL;
+    stride = train_coords[1] - train_coords[0];
+    for (int e = 2; e < n_epochs && loop; ++e) {
+      if (!train_coords[e]) return NDQ_EINVAL;
+      loop = train_coords[e] - train_coords[0] == stride * e;
     }
-    for (int k = f->n_nets; k < 4; ++k) a.net[k] = a.net[0];
-    launch_tail_multi(a, max_params, f->n_nets, max_lparts, st);
-    parity ^= 1;
-    return (int)hipGetLastError();
-  };
-  bool pull = f->pull_ok != 0 && n_epochs >= 2 && s0.blocks * f->n_nets <= ndq::kPullMaxWork && f->alt_loss_partials &&
-              (!valid || f->alt_valid_loss_partials);
-  for (int k = 0; k < f->n_nets && pull; ++k)
-    pull = f->alt_params[k] && f->alt_m[k] && f->alt_v[k] && f->alt_partials[k];
-  if (pull) {
-    // ---- pull mode: ONE launch per epoch.  State of epoch e (parameters, moments) lives in buffer set e & 1; launch e
-    // writes its partial rows into set e & 1 and, in its prologue, finishes epoch e - 1 from set (e - 1) & 1.
-    float* P[2][4]; float* M[2][4]; float* V[2][4]; float* PART[2][4];
-    for (int k = 0; k < f->n_nets; ++k) {
-      P[0][k] = f->net[k].params; M[0][k] = f->net[k].adam_m; V[0][k] = f->net[k].adam_v; PART[0][k] = f->net[k].partials;
-      P[1][k] = f->alt_params[k]; M[1][k] = f->alt_m[k]; V[1][k] = f->alt_v[k]; PART[1][k] = f->alt_partials[k];
-    }
-    float* LP[2] = {s0.loss_partials, f->alt_loss_partials};
-    float* VP[2] = {f->valid_loss_partials, f->alt_valid_loss_partials};
-    const int last = valid ? n_epochs : n_epochs - 1;          // index of the last closure launch
-    int fin = last & 1;                                        // buffer set holding the state after the last closure launch
-    // ---- loop mode: training and validation grid are ONE workgroup each -> runs of up to kLoopMaxLaunches launches of the
-    // sequence below become one launch of one workgroup that keeps the state in LDS (csrc/ndq_tail.h: LoopArgs)
-    bool loop = f->loop_ok != 0 && f->launch_loop && s0.blocks == 1 && (!valid || f->valid_blocks == 1) &&
-                f->n_nets <= ndq::kLoopMaxNets;
-    long long stride = 0;
-    if (loop) {
-      if (!train_coords[0] || !train_coords[1]) return NDQ_EINVAL;
-      stride = train_coords[1] - train_coords[0];
-      for (int e = 2; e < n_epochs && loop; ++e) {
-        if (!train_coords[e]) return NDQ_EINVAL;
-        loop = train_coords[e] - train_coords[0] == stride * e;
-      }
-    }
-    if (loop) {
-      int seg = 0;
-      for (int e0 = 0; e0 <= last; e0 += ndq::kLoopMaxLaunches, ++seg) {
-        const int e1 = e0 + ndq::kLoopMaxLaunches <= last + 1 ? e0 + ndq::kLoopMaxLaunches : last + 1;
-        const int in = seg & 1, out = in ^ 1;
-        ndq::LoopArgs L{};
-        L.e0 = e0; L.e1 = e1; L.n_epochs = n_epochs; L.has_valid = valid ? 1 : 0; L.track_best = f->track_best;
-        L.hist_index = hist_index; L.valid_index = valid_index; L.parity = parity; L.coord_stride = stride;
-        L.lp_in = LP[in]; L.vp_in = VP[in]; L.lp_out = LP[out]; L.vp_out = VP[out];
-        L.lscale = s0.seed; L.vscale = f->valid_scale;
-        L.loss_hist = s0.loss_hist; L.loss_slot = s0.loss_slot; L.valid_hist = f->valid_hist; L.best_loss = s0.best_loss;
-        for (int k = 0; k < f->n_nets; ++k) {
-          const ndq_fused_step& s = f->net[k];
-          ndq::LoopNet& n = L.net[k];
-          n.p_in = P[in][k]; n.m_in = M[in][k]; n.v_in = V[in][k]; n.part_in = PART[in][k];
-          n.p_out = P[out][k]; n.m_out = M[out][k]; n.v_out = V[out][k]; n.part_out = PART[out][k];
-          n.grad = s.grad; n.best_flat = s.best_flat;
-          n.lr = s.lr; n.b1 = s.beta1; n.b2 = s.beta2; n.eps = s.eps; n.wd = s.weight_decay;
-          for (int e = e0 > 1 ? e0 : 1; e < e1; ++e) {         // launch e finishes epoch e - 1: Adam step adam_step + e - 1
-            const int step = adam_step + e - 1;
-            n.bc1[e - e0] = (float)(1.0 - pow((double)s.beta1, (double)step));
-            n.bc2s[e - e0] = (float)sqrt(1.0 - pow((double)s.beta2, (double)step));
-          }
-        }
-        int rc = f->launch_loop(train_coords[0], s0.ldc, s0.n, s0.seed, valid ? f->valid_coords : nullptr, f->valid_ldc,
-                                valid ? f->valid_n : 0, &L, stream);
-        if (rc) return rc;
-        fin = out;
-      }
-      parity ^= (last & 1);
-    }
-    for (int e = 0; e <= last && !loop; ++e) {
-      ndq::PullArgs pa{};
-      if (e >= 1) {                                            // prologue: finish training epoch j = e - 1
-        const int j = e - 1, in = j & 1, out = e & 1;
-        const bool with_valid = valid && j >= 1;                // validation of epoch j - 1, evaluated by launch j
-        pa.enabled = 1; pa.n_nets = f->n_nets; pa.nparts = s0.blocks;
-        pa.lpart = LP[in]; pa.nlparts = s0.blocks; pa.lscale = s0.seed;
-        pa.loss_hist = s0.loss_hist; pa.hist_index = hist_index + j; pa.loss_slot = s0.loss_slot;
-        pa.vpart = with_valid ? VP[in] : nullptr; pa.nvparts = f->valid_blocks; pa.vscale = f->valid_scale;
-        pa.valid_hist = f->valid_hist; pa.valid_index = valid_index + j - 1; pa.best_on_valid = f->track_best == 2 ? 1 : 0;
-        pa.best_loss = s0.best_loss; pa.parity = parity;
-        const bool track = f->track_best == 1 || (f->track_best == 2 && with_valid);
-        for (int k = 0; k < f->n_nets; ++k) {
-          const ndq_fused_step& s = f->net[k];
-          ndq::PullNet& n = pa.net[k];
-          n.part = PART[in][k];
-          n.p_in = P[in][k]; n.m_in = M[in][k]; n.v_in = V[in][k];
-          n.p_out = P[out][k]; n.m_out = M[out][k]; n.v_out = V[out][k];
-          n.grad = s.grad; n.best_flat = track ? s.best_flat : nullptr; n.len = s.n_params;
-          const int step = adam_step + j;
-          n.adam = ndq::AdamConsts{s.lr, s.beta1, s.beta2, s.eps, s.weight_decay,
-                                   (float)(1.0 - pow((double)s.beta1, (double)step)),
-                                   (float)sqrt(1.0 - pow((double)s.beta2, (double)step))};
-        }
-        parity ^= 1;
-      }
-      const bool train_part = e < n_epochs, valid_part = valid && e >= 1;
-      if (train_part && !train_coords[e]) return NDQ_EINVAL;
-      const float* pp[4]; float* qq[4];
-      for (int k = 0; k < f->n_nets; ++k) { pp[k] = P[e & 1][k]; qq[k] = PART[e & 1][k]; }
-      int rc = f->launch(train_part ? train_coords[e] : nullptr, s0.ldc, train_part ? s0.n : 0, pp, train_part ? qq : nullptr,
-                         LP[e & 1], s0.seed, valid_part ? f->valid_coords : nullptr, f->valid_ldc, valid_part ? f->valid_n : 0,
-                         VP[e & 1], &pa, stream);
-      if (rc) return rc;
-    }
-    // ---- the call's last launch: an ordinary tail that leaves everything in the primary buffers
-    ReduceTailMultiArgs a{};
-    for (int k = 0; k < f->n_nets; ++k) {
-      const ndq_fused_step& s = f->net[k];
-      ReduceTailArgs& t = a.net[k];
-      t.t.p = s.params; t.t.g = s.grad; t.t.m = s.adam_m; t.t.v = s.adam_v; t.t.len = s.n_params;
-      t.t.lr = s.lr; t.t.b1 = s.beta1; t.t.b2 = s.beta2; t.t.eps = s.eps; t.t.wd = s.weight_decay;
-      t.t.loss_slots = s.loss_slot; t.t.nb = 1; t.t.loss_hist = s0.loss_hist; t.t.best_loss = s0.best_loss; t.t.parity = parity;
-      t.t.write_scalars = (k == 0) ? 1 : 0;
-      t.tail_blocks = 0x7fffffff;
-      t.t.p_in = fin ? P[fin][k] : nullptr; t.t.m_in = fin ? M[fin][k] : nullptr; t.t.v_in = fin ? V[fin][k] : nullptr;
-      if (valid) {              // validation of the last epoch (evaluated by the trailing launch); no Adam
-        t.r = Reduce2Args{PART[fin][k], 0, s.n_params, s.grad, 0, LP[fin], 0, s.loss_slot, s0.seed};
-        t.t.bc1 = 1.f; t.t.bc2s = 1.f; t.t.hist_index = hist_index + n_epochs - 1;
-        t.t.best_flat = f->track_best == 2 ? s.best_flat : nullptr;
-        t.v = ValidArgs{VP[fin], f->valid_blocks, f->valid_scale, f->valid_hist, valid_index + n_epochs - 1,
-                        f->track_best == 2 ? 1 : 0};
-      } else {                  // the last training epoch's update
-        const int step = adam_step + n_epochs - 1;
-        t.r = Reduce2Args{PART[fin][k], s0.blocks, s.n_params, s.grad, 0, LP[fin], s0.blocks, s.loss_slot, s0.seed};
-        t.t.bc1 = (float)(1.0 - pow((double)s.beta1, (double)step));
-        t.t.bc2s = (float)sqrt(1.0 - pow((double)s.beta2, (double)step));
-        t.t.hist_index = hist_index + n_epochs - 1;
-        t.t.best_flat = f->track_best == 1 ? s.best_flat : nullptr;
-      }
-    }
-    for (int k = f->n_nets; k < 4; ++k) a.net[k] = a.net[0];
-    launch_tail_multi(a, max_params, f->n_nets, max_lparts, st);
-    return (int)hipGetLastError();
   }
-  for (int e = 0; e < n_epochs; ++e) {
-    if (!train_coords[e]) return NDQ_EINVAL;
-    const bool with_valid = valid && e > 0;
-    int rc = f->launch(train_coords[e], s0.ldc, s0.n, params, partials, s0.loss_partials, s0.seed,
-                       with_valid ? f->valid_coords : nullptr, f->valid_ldc, with_valid ? f->valid_n : 0,
-                       f->valid_loss_partials, nullptr, stream);
-    if (rc) return rc;
-    rc = tail(e, true, with_valid, valid_index + e - 1);
-    if (rc) return rc;
-  }
-  if (valid) {
-    int rc = f->launch(nullptr, 0, 0, params, nullptr, nullptr, 0.f, f->valid_coords, f->valid_ldc, f->valid_n,
-                       f->valid_loss_partials, nullptr, stream);
-    if (rc) return rc;
-    rc = tail(n_epochs, false, true, valid_index + (n_epochs > 0 ? n_epochs - 1 : 0));
-    if (rc) return rc;
-  }
-  return 0;
+  return loop ? fit_loop(c, stride, parity) : fit_pull(c, parity);
 }
 
 int ndq_adam_step(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int len, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int step, void* stream) {
   if (!params || !grad || !exp_avg || !exp_avg_sq || len <= 0 || step <= 0) return NDQ_EINVAL;
-  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  hipLaunchKernelGGL(adam_kernel, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), params, grad,
-                     exp_avg, exp_avg_sq, len, lr, beta1, beta2, eps, weight_decay, bc1, bc2s);
+  hipLaunchKernelGGL(adam_kernel<float>, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), params, grad,
+                     exp_avg, exp_avg_sq, len, adam_consts(lr, beta1, beta2, eps, weight_decay, step));
   return (int)hipGetLastError();
 }
 

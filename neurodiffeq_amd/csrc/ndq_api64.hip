@@ -21,27 +21,16 @@ namespace ndq {
 static const ndq64_mlp_kernels kTable64[] = {NDQ64_CFG_TABLE(NDQ64_ENTRY)};
 static std::vector<const ndq64_mlp_kernels*> g_registered64;
 
-static bool same_desc(const ndq_mlp_desc& a, const ndq_mlp_desc& b) {
-  return a.d == b.d && a.first == b.first && a.mask2 == b.mask2 && a.hidden == b.hidden && a.layers == b.layers &&
-         a.act == b.act && a.n_out == b.n_out && a.lap == b.lap && a.skip == b.skip && a.mask3 == b.mask3 && a.mask4 == b.mask4 &&
-         a.actp == b.actp && a.widths == b.widths && a.mono == b.mono;
-}
+// (hidden > 64: ONE hidden layer of up to 512 units -- csrc/ndq_wide.h compiled in double, registered extension modules only)
+static bool hidden_ok64(const ndq_mlp_desc& d) { return d.hidden >= 1 && d.hidden <= (d.layers == 1 ? 512 : 64); }
 
 static const ndq64_mlp_kernels* find64(const ndq_mlp_desc* d) {
-  // (hidden > 64: ONE hidden layer of up to 512 units -- csrc/ndq_wide.h compiled in double, registered extension modules only)
-  if (!d || d->hidden < 1 || d->hidden > (d->layers == 1 ? 512 : 64)) return nullptr;
+  if (!d || !hidden_ok64(*d)) return nullptr;
   for (const ndq64_mlp_kernels& e : kTable64)
     if (same_desc(e.desc, *d)) return &e;
   for (const ndq64_mlp_kernels* e : g_registered64)
     if (same_desc(e->desc, *d)) return e;
   return nullptr;
-}
-
-static int bwd_blocks64(const ndq64_mlp_kernels* e, int n) {
-  const int tiles = (n + 15) / 16;
-  int blocks = (tiles + e->bwd_waves - 1) / e->bwd_waves;
-  if (blocks > NDQ_BWD_MAX_BLOCKS) blocks = NDQ_BWD_MAX_BLOCKS;
-  return blocks < 1 ? 1 : blocks;
 }
 
 // out[i] = (acc ? out[i] : 0) + scale * sum_r partials[r*len + i], rows in fixed order.  A workgroup owns 64 columns; its
@@ -94,57 +83,6 @@ __global__ __launch_bounds__(1024) void reduce_partials64_kernel(const double* _
   }
 }
 
-// torch.optim.Adam (amsgrad=False, maximize=False), the fp32 kernel of ndq_api.hip in double
-__global__ __launch_bounds__(256) void adam64_kernel(double* __restrict__ p, const double* __restrict__ g,
-                                                     double* __restrict__ m, double* __restrict__ v, int len, double lr,
-                                                     double b1, double b2, double eps, double wd, double bc1, double bc2s) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= len) return;
-  double gi = g[i];
-  const double pi = p[i];
-  if (wd != 0.0) gi = fma(wd, pi, gi);
-  const double mi = fma(b1, m[i], (1.0 - b1) * gi);
-  const double vi = fma(b2, v[i], (1.0 - b2) * gi * gi);
-  m[i] = mi;
-  v[i] = vi;
-  p[i] = pi - (lr / bc1) * (mi / (sqrt(vi) / bc2s + eps));
-}
-
-// Device-side end of an fp64 epoch, the double twin of ndq_api.hip's epoch_tail_kernel: mean of the per-batch losses ->
-// history ring, best-loss ping-pong + snapshot of the parameters the epoch was evaluated on, Adam (the arithmetic of
-// adam64_kernel, operation for operation: an epoch through this kernel and one through ndq64_adam_step agree bit for bit).
-struct Tail64Args {
-  double* p; const double* g; double* m; double* v; int len;
-  double lr, b1, b2, eps, wd, bc1, bc2s;
-  const double* loss_slots; int nb; double* loss_hist; int hist_index; double* best_loss; int parity; double* best_flat;
-  int write_scalars;
-};
-__global__ __launch_bounds__(256) void epoch_tail64_kernel(Tail64Args a) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  double loss = 0.;
-  for (int k = 0; k < a.nb; ++k) loss += a.loss_slots[k];
-  loss /= (double)a.nb;
-  const double best = a.best_loss[a.parity];
-  const bool better = (a.best_flat != nullptr) && (loss < best);   // false for NaN, like the reference's comparison
-  if (i < a.len) {
-    const double pi = a.p[i];
-    if (better) a.best_flat[i] = pi;
-    if (a.m != nullptr) {             // validation epochs pass no optimiser state: bookkeeping only
-      double gi = a.g[i];
-      if (a.wd != 0.0) gi = fma(a.wd, pi, gi);
-      const double mi = fma(a.b1, a.m[i], (1.0 - a.b1) * gi);
-      const double vi = fma(a.b2, a.v[i], (1.0 - a.b2) * gi * gi);
-      a.m[i] = mi;
-      a.v[i] = vi;
-      a.p[i] = pi - (a.lr / a.bc1) * (mi / (sqrt(vi) / a.bc2s + a.eps));
-    }
-  }
-  if (i == 0 && a.write_scalars) {
-    a.loss_hist[a.hist_index] = loss;
-    a.best_loss[a.parity ^ 1] = better ? loss : best;
-  }
-}
-
 }  // namespace ndq
 
 using namespace ndq;
@@ -154,7 +92,7 @@ extern "C" {
 int ndq64_mlp_supported(const ndq_mlp_desc* desc) { return find64(desc) ? 1 : 0; }
 
 int ndq64_mlp_register(const ndq64_mlp_kernels* k) {
-  if (!k || !k->fwd || !k->bwd || k->desc.hidden < 1 || k->desc.hidden > (k->desc.layers == 1 ? 512 : 64) || k->n_streams < 1 || k->n_params < 1 || k->bwd_waves < 1 ||
+  if (!k || !k->fwd || !k->bwd || !hidden_ok64(k->desc) || k->n_streams < 1 || k->n_params < 1 || k->bwd_waves < 1 ||
       k->lds_bytes > 160 * 1024)
     return NDQ_EINVAL;
   if (!find64(&k->desc)) g_registered64.push_back(k);
@@ -175,7 +113,7 @@ int ndq64_mlp_bwd_blocks(const ndq_mlp_desc* desc, int n) {
   const ndq64_mlp_kernels* e = find64(desc);
   if (!e) return NDQ_EUNSUPPORTED;
   if (n <= 0) return NDQ_EINVAL;
-  return bwd_blocks64(e, n);
+  return bwd_blocks(e->bwd_waves, n);
 }
 
 int ndq64_mlp_jet_fwd(const ndq_mlp_desc* desc, const double* coords, int ldc, int n, const double* params, double* jets,
@@ -191,7 +129,7 @@ int ndq64_mlp_jet_bwd(const ndq_mlp_desc* desc, const double* coords, int ldc, i
   const ndq64_mlp_kernels* e = find64(desc);
   if (!e) return NDQ_EUNSUPPORTED;
   if (!coords || !params || !gbar || !partials || n <= 0 || ldc < n || ldj < n) return NDQ_EINVAL;
-  return e->bwd(coords, ldc, n, params, gbar, ldj, partials, bwd_blocks64(e, n), stream);
+  return e->bwd(coords, ldc, n, params, gbar, ldj, partials, bwd_blocks(e->bwd_waves, n), stream);
 }
 
 int ndq64_reduce_partials(const double* partials, int nparts, int len, double* out, int accumulate, double scale,
@@ -202,12 +140,13 @@ int ndq64_reduce_partials(const double* partials, int nparts, int len, double* o
   return (int)hipGetLastError();
 }
 
+// Adam and the device-side end of an fp64 epoch: ndq_tail.h's adam_kernel / epoch_tail_kernel instantiated for double -- the
+// source libndq.so runs in float, so an epoch through ndq64_epoch_tail and one through ndq64_adam_step agree bit for bit
 int ndq64_adam_step(double* params, const double* grad, double* exp_avg, double* exp_avg_sq, int len, double lr,
                     double beta1, double beta2, double eps, double weight_decay, int step, void* stream) {
   if (!params || !grad || !exp_avg || !exp_avg_sq || len <= 0 || step <= 0) return NDQ_EINVAL;
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2s = sqrt(1.0 - pow(beta2, (double)step));
-  hipLaunchKernelGGL(adam64_kernel, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), params, grad,
-                     exp_avg, exp_avg_sq, len, lr, beta1, beta2, eps, weight_decay, bc1, bc2s);
+  hipLaunchKernelGGL(adam_kernel<double>, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), params, grad,
+                     exp_avg, exp_avg_sq, len, adam_consts(lr, beta1, beta2, eps, weight_decay, step));
   return (int)hipGetLastError();
 }
 
@@ -219,14 +158,12 @@ int ndq64_epoch_tail(double* params, const double* grad, double* exp_avg, double
   if (!params || len <= 0 || !loss_slots || n_batches <= 0 || !loss_hist || !best_loss || hist_index < 0 ||
       (parity != 0 && parity != 1) || (adam && (!grad || !exp_avg_sq || step <= 0)))
     return NDQ_EINVAL;
-  Tail64Args a{};
+  TailArgsT<double> a{};
   a.p = params; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.len = len;
-  a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay;
-  a.bc1 = adam ? 1.0 - pow(beta1, (double)step) : 1.0;
-  a.bc2s = adam ? sqrt(1.0 - pow(beta2, (double)step)) : 1.0;
+  a.adam = adam_consts(lr, beta1, beta2, eps, weight_decay, adam ? step : 0);
   a.loss_slots = loss_slots; a.nb = n_batches; a.loss_hist = loss_hist; a.hist_index = hist_index;
   a.best_loss = best_loss; a.parity = parity; a.best_flat = best_flat; a.write_scalars = write_scalars;
-  hipLaunchKernelGGL(epoch_tail64_kernel, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(epoch_tail_kernel<double>, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
 }
 

@@ -22,6 +22,20 @@ namespace ndq {
 #define NDQ_BWD_MAX_BLOCKS 256   // one workgroup per CU; every wave amortises its epilogue over several tiles
 #endif
 
+// descriptor dispatch of libndq.so / libndq64.so: two descriptors name the same kernels
+inline bool same_desc(const ndq_mlp_desc& a, const ndq_mlp_desc& b) {
+  return a.d == b.d && a.first == b.first && a.mask2 == b.mask2 && a.hidden == b.hidden && a.layers == b.layers &&
+         a.act == b.act && a.n_out == b.n_out && a.lap == b.lap && a.skip == b.skip && a.mask3 == b.mask3 && a.mask4 == b.mask4 &&
+         a.actp == b.actp && a.widths == b.widths && a.mono == b.mono;
+}
+// workgroups (= partial rows) of an adjoint launch over n points: one 16-point tile per wave and iteration
+inline int bwd_blocks(int bwd_waves, int n) {
+  const int tiles = (n + 15) / 16;
+  int blocks = (tiles + bwd_waves - 1) / bwd_waves;
+  if (blocks > NDQ_BWD_MAX_BLOCKS) blocks = NDQ_BWD_MAX_BLOCKS;
+  return blocks < 1 ? 1 : blocks;
+}
+
 template <class C>
 int launch_fwd(const MlpArgs& a, hipStream_t s) {
   static bool attr = false;

@@ -8,8 +8,11 @@
 //     them.  Used for small grids only (every workgroup reads every partial row: <= 32 rows).
 // Both routes perform the SAME floating-point operations in the SAME order (the summation orders of the tail kernel are
 // spelled out below and re-enacted by the prologue), so a training run does not depend on which one served an epoch.
+// Also here, because libndq.so and libndq64.so share them: adam_value<T> / adam_consts (the one Adam of the package, float
+// and double) and, at the end, the kernels behind ndq[64]_epoch_tail / ndq[64]_adam_step (epoch_tail_kernel<T>, adam_kernel<T>).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 
 namespace ndq {
 
@@ -20,15 +23,25 @@ constexpr int kPullMaxRows = 32;        // partial rows (closure workgroups) the
 constexpr int kPullMaxWork = 16;
 constexpr int kPullMaxNets = 4;
 
-// Adam, torch.optim.Adam single-tensor formula (amsgrad = False, maximize = False); bc1 = 1 - b1^t, bc2s = sqrt(1 - b2^t)
-struct AdamConsts { float lr, b1, b2, eps, wd, bc1, bc2s; };
-__device__ __forceinline__ void adam_value(const AdamConsts& c, float pi, float g, float m0, float v0, float& p, float& m,
-                                           float& v) {
-  float gi = g;
-  if (c.wd != 0.f) gi = fmaf(c.wd, pi, gi);
-  m = fmaf(c.b1, m0, (1.f - c.b1) * gi);
-  v = fmaf(c.b2, v0, (1.f - c.b2) * gi * gi);
-  p = pi - (c.lr / c.bc1) * (m / (sqrtf(v) / c.bc2s + c.eps));
+// Adam, torch.optim.Adam single-tensor formula (amsgrad = False, maximize = False); bc1 = 1 - b1^t, bc2s = sqrt(1 - b2^t):
+//   g += wd p; m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g^2; p -= lr / bc1 * m / (sqrt(v) / bc2s + eps)
+// ONE definition for every kernel of the package, in float (fmaf / sqrtf) and in double (fma / sqrt).
+template <class T> struct AdamConstsT { T lr, b1, b2, eps, wd, bc1, bc2s; };
+using AdamConsts = AdamConstsT<float>;
+template <class T>
+__device__ __forceinline__ void adam_value(const AdamConstsT<T>& c, T pi, T g, T m0, T v0, T& p, T& m, T& v) {
+  T gi = g;
+  if (c.wd != T(0)) gi = fma(c.wd, pi, gi);
+  m = fma(c.b1, m0, (T(1) - c.b1) * gi);
+  v = fma(c.b2, v0, (T(1) - c.b2) * gi * gi);
+  p = pi - (c.lr / c.bc1) * (m / (sqrt(v) / c.bc2s + c.eps));
+}
+// host: the constants of update number `step` -- bias corrections computed in double and narrowed to T; step <= 0 (a launch
+// without an optimiser step, e.g. a validation tail): 1 / 1
+template <class T>
+inline AdamConstsT<T> adam_consts(T lr, T b1, T b2, T eps, T wd, int step) {
+  if (step <= 0) return {lr, b1, b2, eps, wd, T(1), T(1)};
+  return {lr, b1, b2, eps, wd, (T)(1.0 - pow((double)b1, (double)step)), (T)sqrt(1.0 - pow((double)b2, (double)step))};
 }
 
 // ---- the tail kernel's summation orders, re-enacted ------------------------------------------------------------------
@@ -398,5 +411,54 @@ __device__ __forceinline__ void loop_pull_args(const LoopArgs& L, int e, float* 
   }
 }
 
+
+// ---- epoch tail without the sums, and Adam alone (ndq_epoch_tail / ndq_adam_step and their fp64 twins) ------------------
+// The end of an epoch whose per-batch losses and reduced gradient are already in memory: mean of the loss slots -> history
+// ring, best-loss ping-pong + snapshot of the parameters the epoch was evaluated on, adam_value.  One source for libndq.so
+// (T = float) and libndq64.so (T = double); ndq_api.hip's sums + tail kernels embed the same struct.
+template <class T> struct TailArgsT {
+  T* p; const T* g; T* m; T* v; int len;
+  AdamConstsT<T> adam;
+  // where the parameters / moments this epoch started from live, when that is not p / m / v (fit() in pull mode keeps
+  // two sets of buffers; the tail that closes a call brings the result home): nullptr = in place.  (sums + tail kernels only)
+  const T* p_in; const T* m_in; const T* v_in;
+  const T* loss_slots; int nb; T* loss_hist; int hist_index; T* best_loss; int parity; T* best_flat;
+  int write_scalars;
+};
+template <class T>
+__global__ __launch_bounds__(256) void epoch_tail_kernel(TailArgsT<T> a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  T loss = T(0);
+  for (int k = 0; k < a.nb; ++k) loss += a.loss_slots[k];
+  loss /= (T)a.nb;
+  const T best = a.best_loss[a.parity];
+  const bool better = (a.best_flat != nullptr) && (loss < best);   // false for NaN, like the reference's comparison
+  if (i < a.len) {
+    const T pi = a.p[i];
+    if (better) a.best_flat[i] = pi;
+    if (a.m != nullptr) {             // validation epochs pass no optimiser state: bookkeeping only
+      T pn, mi, vi;
+      adam_value(a.adam, pi, a.g[i], a.m[i], a.v[i], pn, mi, vi);
+      a.m[i] = mi;
+      a.v[i] = vi;
+      a.p[i] = pn;
+    }
+  }
+  if (i == 0 && a.write_scalars) {
+    a.loss_hist[a.hist_index] = loss;
+    a.best_loss[a.parity ^ 1] = better ? loss : best;
+  }
+}
+template <class T>
+__global__ __launch_bounds__(256) void adam_kernel(T* __restrict__ p, const T* __restrict__ g, T* __restrict__ m,
+                                                   T* __restrict__ v, int len, AdamConstsT<T> c) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= len) return;
+  T pn, mi, vi;
+  adam_value(c, p[i], g[i], m[i], v[i], pn, mi, vi);
+  m[i] = mi;
+  v[i] = vi;
+  p[i] = pn;
+}
 
 }  // namespace ndq

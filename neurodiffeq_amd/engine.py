@@ -1051,6 +1051,31 @@ class FusedSystem:
                               pending_valid=0, structs={})
         return self._fast
 
+    def _fill_step(self, st, k, n, ld, blocks, partials, loss_partials):
+        """The batch-invariant fields of network k's ``_lib.FusedStep``: sizes, partial rows, where the reduced gradient,
+        the epoch loss and the epoch bookkeeping go."""
+        fs, fp = self.fast_state(), self.flat[k]
+        st.n, st.ldc, st.ldj, st.blocks, st.n_params = n, ld, ld, blocks, fp.numel
+        if partials is not None:
+            st.partials, st.loss_partials = partials.data_ptr(), loss_partials.data_ptr()
+        st.grad, st.loss_slot = fp.grad.data_ptr(), fp.grad_loss.data_ptr() + 4 * fp.numel
+        st.loss_hist, st.best_loss = fs["loss_hist"].data_ptr(), fs["best_loss"].data_ptr()
+
+    @staticmethod
+    def _set_adam(st, m, v, group):
+        """An Adam slot (FusedAdam.fast_slot: moments + parameter group) into a ``_lib.FusedStep``."""
+        st.adam_m, st.adam_v = m.data_ptr(), v.data_ptr()
+        (st.beta1, st.beta2), st.lr, st.eps, st.weight_decay = group["betas"], group["lr"], group["eps"], group["weight_decay"]
+
+    @staticmethod
+    def _tail_args(fp, adam_slot):
+        """The leading arguments of ndq_epoch_tail for one network: parameters, gradient, Adam slot (None: a validation epoch)."""
+        if adam_slot is None:
+            return _ptr(fp.flat), None, None, None, fp.numel, 0.0, 0.0, 0.0, 0.0, 0.0, 1
+        m, v, group, step = adam_slot
+        return (_ptr(fp.flat), _ptr(fp.grad), _ptr(m), _ptr(v), fp.numel, group["lr"], *group["betas"], group["eps"],
+                group["weight_decay"], step)
+
     def epoch_tail(self, kind, n_batches, track_best, adam_slots=None):
         """Device-side end of an epoch for ANY fused system (pipeline or single-launch), after the per-batch
         ``step()`` calls filled ``loss_buf[:n_batches]`` and the gradient buffers: mean loss -> history ring, best
@@ -1064,13 +1089,7 @@ class FusedSystem:
         parity = fs["parity"]
         for k, fp in enumerate(self.flat):
             fp.sync()
-            if train:
-                m, v, group, step = adam_slots[k]
-                b1, b2 = group["betas"]
-                args = (_ptr(fp.flat), _ptr(fp.grad), _ptr(m), _ptr(v), fp.numel, group["lr"], b1, b2, group["eps"],
-                        group["weight_decay"], step)
-            else:
-                args = (_ptr(fp.flat), None, None, None, fp.numel, 0.0, 0.0, 0.0, 0.0, 0.0, 1)
+            args = self._tail_args(fp, adam_slots[k] if train else None)
             rc = self.L.ndq_epoch_tail(*args, _ptr(self.loss_buf), n_batches, _ptr(hist), idx, _ptr(fs["best_loss"]),
                                        parity, _ptr(fs["best_flat"][k]) if track_best else None, 1 if k == 0 else 0,
                                        stream)
@@ -1091,12 +1110,8 @@ class FusedSystem:
         arr = fs["structs"].get(key)
         if arr is None:
             arr = (_lib.FusedStep * K)()
-            for k, fp in enumerate(self.flat):
-                st = arr[k]
-                st.n, st.ldc, st.ldj, st.blocks, st.n_params = n, b["ld"], b["ld"], b["fused_blocks"], fp.numel
-                st.partials, st.loss_partials = b["fused_partials_all"][k].data_ptr(), b["fused_loss_partials"].data_ptr()
-                st.grad, st.loss_slot = fp.grad.data_ptr(), fp.grad_loss.data_ptr() + 4 * fp.numel
-                st.loss_hist, st.best_loss = fs["loss_hist"].data_ptr(), fs["best_loss"].data_ptr()
+            for k in range(K):
+                self._fill_step(arr[k], k, n, b["ld"], b["fused_blocks"], b["fused_partials_all"][k], b["fused_loss_partials"])
             fs["structs"][key] = arr
         step = None
         for k, fp in enumerate(self.flat):
@@ -1107,9 +1122,7 @@ class FusedSystem:
             st.params = fp.flat.data_ptr()
             st.seed = 1.0 / (float(n) * self.loss_norm)
             st.best_flat = fs["best_flat"][k].data_ptr() if track_best else None
-            st.adam_m, st.adam_v = m.data_ptr(), v.data_ptr()
-            b1, b2 = group["betas"]
-            st.lr, st.beta1, st.beta2, st.eps, st.weight_decay = group["lr"], b1, b2, group["eps"], group["weight_decay"]
+            self._set_adam(st, m, v, group)
         rc = self.L.ndq_fused_multi_step_run(arr, K, _c_vp(b["fused_launch_multi"]), self._coord_ptr(b, 0), step,
                                              fs["pending"], fs["parity"], self._stream())
         _lib.check(rc, "ndq_fused_multi_step_run")
@@ -1130,17 +1143,13 @@ class FusedSystem:
         if st is None:
             st = _lib.FusedStep()
             st.launch = b["fused_launch"]
-            st.n, st.ldc, st.ldj, st.blocks, st.n_params = n, b["ld"], b["ld"], b["fused_blocks"], fp.numel
-            st.partials, st.loss_partials = b["fused_partials"].data_ptr(), b["fused_loss_partials"].data_ptr()
-            st.grad, st.loss_slot = fp.grad.data_ptr(), fp.grad_loss.data_ptr() + 4 * fp.numel
-            st.loss_hist, st.best_loss = fs["loss_hist"].data_ptr(), fs["best_loss"].data_ptr()
+            self._fill_step(st, 0, n, b["ld"], b["fused_blocks"], b["fused_partials"], b["fused_loss_partials"])
             fs["structs"][key] = st
         n_global = n if n_global is None else n_global
         st.params = fp.flat.data_ptr()
         st.seed = 1.0 / (float(n_global) * self.loss_norm)
         st.best_flat = fs["best_flat"][0].data_ptr() if track_best else None
-        b1, b2 = group["betas"]
-        st.lr, st.beta1, st.beta2, st.eps, st.weight_decay = group["lr"], b1, b2, group["eps"], group["weight_decay"]
+        self._set_adam(st, m, v, group)
         stream = self._stream()
         coords = self._coord_ptr(b, 0)
         hist_index, parity = fs["pending"], fs["parity"]
@@ -1158,7 +1167,6 @@ class FusedSystem:
         if dist is None or direct is not None:
             # one native call; with data parallelism the RCCL all-reduce of [grad | loss] is enqueued by it, on the
             # same stream, between the local sums and the tail
-            st.adam_m, st.adam_v = m.data_ptr(), v.data_ptr()
             st.allreduce, st.comm = direct if direct is not None else (None, None)
             rc = self.L.ndq_fused_step_run(ctypes.byref(st), coords, step, hist_index, parity, stream)
             _lib.check(rc, "ndq_fused_step_run")
@@ -1170,9 +1178,8 @@ class FusedSystem:
             rc = self.L.ndq_fused_step_run(ctypes.byref(st), coords, step, hist_index, parity, stream)
             _lib.check(rc, "ndq_fused_step_run")
             dist.all_reduce_flat(fp.grad_loss)
-            rc = self.L.ndq_epoch_tail(_ptr(fp.flat), _ptr(fp.grad), _ptr(m), _ptr(v), fp.numel, group["lr"], b1, b2,
-                                       group["eps"], group["weight_decay"], step, _c_vp(st.loss_slot), 1,
-                                       _ptr(fs["loss_hist"]), hist_index, _ptr(fs["best_loss"]), parity,
+            rc = self.L.ndq_epoch_tail(*self._tail_args(fp, adam_slot), _c_vp(st.loss_slot), 1, _ptr(fs["loss_hist"]),
+                                       hist_index, _ptr(fs["best_loss"]), parity,
                                        _ptr(fs["best_flat"][0]) if track_best else None, 1, stream)
             _lib.check(rc, "ndq_epoch_tail")
         fs["pending"] += 1
@@ -1261,16 +1268,10 @@ class FusedSystem:
             lparts = torch.zeros(max(blocks, 1), dtype=f32, device=dev)
             keep.append(lparts)
             for k, fp in enumerate(self.flat):
-                st = ff.net[k]
-                st.n_params = fp.numel
-                st.n, st.ldc, st.ldj, st.blocks = (n, ld, ld, blocks) if K else (0, 0, 0, 0)
-                if K:
-                    part = torch.empty(blocks, fp.numel, dtype=f32, device=dev)
-                    keep.append(part)
-                    st.partials, st.loss_partials = part.data_ptr(), lparts.data_ptr()
-                st.grad, st.loss_slot = fp.grad.data_ptr(), fp.grad_loss.data_ptr() + 4 * fp.numel
-                st.loss_hist, st.best_loss = fs["loss_hist"].data_ptr(), fs["best_loss"].data_ptr()
-                st.best_flat = fs["best_flat"][k].data_ptr()
+                part = torch.empty(blocks, fp.numel, dtype=f32, device=dev) if K else None
+                keep.append(part)
+                self._fill_step(ff.net[k], k, *((n, ld, blocks) if K else (0, 0, 0)), part, lparts)
+                ff.net[k].best_flat = fs["best_flat"][k].data_ptr()
             if valid is not None:
                 vparts = torch.zeros(fk.blocks(valid[1]), dtype=f32, device=dev)
                 keep.append(vparts)
@@ -1320,9 +1321,7 @@ class FusedSystem:
                 st.params = now[0]
                 if K:
                     st.seed = 1.0 / (float(now[1]) * self.loss_norm)
-                    st.adam_m, st.adam_v = now[2], now[3]
-                    b1, b2 = group["betas"]
-                    st.lr, st.beta1, st.beta2, st.eps, st.weight_decay = group["lr"], b1, b2, group["eps"], group["weight_decay"]
+                    self._set_adam(st, m, v, group)
         vc = valid[0] if valid is not None else None
         if last.get("v") != (vc, track_best):
             last["v"] = (vc, track_best)

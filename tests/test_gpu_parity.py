@@ -396,6 +396,52 @@ def test_adam_step_matches_torch(L):
     assert rel_l2(p.cpu().numpy(), ref.detach().numpy()) < 1e-6
 
 
+def _check_epoch_tail_is_adam_step(n):
+    """ndq_epoch_tail's Adam against ndq_adam_step (and the ndq64_ pair), array for array, plus the tail's bookkeeping: mean
+    of the loss slots -> history, best-loss ping-pong, snapshot of the PRE-update parameters."""
+    from neurodiffeq_amd import _lib
+    hyper = (1e-3, 0.9, 0.999, 1e-8, 0.01)                      # lr, betas, eps, weight_decay
+    for pre, lib, dt in (("ndq_", _lib.lib(), torch.float32), ("ndq64_", _lib.lib64(), torch.float64)):
+        adam_step, epoch_tail = getattr(lib, pre + "adam_step"), getattr(lib, pre + "epoch_tail")
+        rng = np.random.default_rng(7)
+        p0, g, m0 = (torch.from_numpy(rng.standard_normal(n)).to(dt).cuda() for _ in range(3))
+        v0 = torch.from_numpy(rng.standard_normal(n) ** 2).to(dt).cuda()
+        pa, ma, va = p0.clone(), m0.clone(), v0.clone()
+        assert adam_step(pa.data_ptr(), g.data_ptr(), ma.data_ptr(), va.data_ptr(), n, *hyper, 3, _stream()) == 0
+        pb, mb, vb = p0.clone(), m0.clone(), v0.clone()
+        slots = torch.tensor([0.75, 0.25], dtype=dt, device="cuda")
+        hist = torch.zeros(8, dtype=dt, device="cuda")
+        best = torch.full((2,), float("inf"), dtype=dt, device="cuda")
+        snap = torch.zeros(n, dtype=dt, device="cuda")
+
+        def tail(moments, step, hist_index, parity):
+            mp, vp = (None, None) if moments is None else (moments[0].data_ptr(), moments[1].data_ptr())
+            assert epoch_tail(pb.data_ptr(), g.data_ptr(), mp, vp, n, *hyper, step, slots.data_ptr(), 2, hist.data_ptr(),
+                              hist_index, best.data_ptr(), parity, snap.data_ptr(), 1, _stream()) == 0
+            torch.cuda.synchronize()
+
+        tail((mb, vb), 3, 5, 0)
+        for got, want in ((pb, pa), (mb, ma), (vb, va)):
+            assert torch.equal(got, want), pre
+        assert hist[5].item() == 0.5 and best[1].item() == 0.5 and torch.equal(snap, p0), pre
+        slots.fill_(2.0)                                          # a worse epoch: best value and snapshot stay
+        tail((mb, vb), 4, 6, 1)
+        assert hist[6].item() == 2.0 and best[0].item() == 0.5 and torch.equal(snap, p0), pre
+        assert not torch.equal(pb, pa)
+        p1, m1, v1 = pb.clone(), mb.clone(), vb.clone()
+        tail(None, 1, 7, 0)                                       # a validation epoch: no optimiser state, bookkeeping only
+        assert torch.equal(pb, p1) and torch.equal(mb, m1) and torch.equal(vb, v1), pre
+        assert hist[7].item() == 2.0 and best[1].item() == 0.5 and torch.equal(snap, p0), pre
+
+
+def test_epoch_tail_adam_is_adam_step_bitwise(L):
+    _check_epoch_tail_is_adam_step(257)         # two 256-thread workgroups, the second with one live lane
+
+
+def test_epoch_tail_adam_is_adam_step_bitwise_single_element(L):
+    _check_epoch_tail_is_adam_step(1)           # the degenerate grid
+
+
 # ------------------------------------------------------------------------------------------------ whole closure
 def _load_system(name, size, single_kernel=True):
     from tests import configs
