@@ -149,6 +149,34 @@ typedef struct ndq_sampler_desc {
 int ndq_sample(const ndq_sampler_desc* desc, unsigned long long seed, unsigned long long draw, unsigned stream_id,
                float* coords, int ldc, void* stream);
 
+/* Table sampler: every axis of an ij-meshgrid (last axis fastest) reads its node positions and jitter widths from small
+ * device tables, so any spacing the host can tabulate -- GeneratorND's 'equally-spaced' / 'uniform' / 'log-spaced' /
+ * 'exp-spaced' / 'chebyshev*' axes with `cut` and `abs_value` (generators.py:419-569), Generator1D 'log-spaced[-noisy]'
+ * and 'chebyshev*' -- is drawn by one kernel, for up to six coordinates.
+ * Point i (one thread): Philox block A = counter (i, draw_lo, draw_hi, stream_id) under key `seed`, the block ndq_sample
+ * uses; axes 0..2 take their normals from it exactly as NDQ_SAMPLE_GRID does (z0 = r0 cos t0, z1 = r0 sin t0,
+ * z2 = r1 cos t1).  Axes 3..5 take theirs the same way from block B, whose counter word 0 is i | 0x80000000: the number
+ * of points is capped at 2^31 - 1, so no point of any draw or stream owns that word.  Block B is computed only for d > 3.
+ * NORMAL axis c:   v = mean[c][idx_c]; if std[c] != NULL and std[c][idx_c] != 0: v = fma(std[c][idx_c], z_c, v);
+ *                  abs_value: v = |v|.  Without jitter v is the table entry bit for bit.
+ * CHEB2_NOISY:     v = ((lo + hi) + (hi - lo) * cos((i + (2 U[0,1)(w0) - 1)) / (n - 1) * pi)) / 2   (generators.py:32-34)
+ * NDQ_EINVAL (nothing launched): d outside 1..6, an n[c] < 1, more than 2^31 - 1 points, ldc < points, a NORMAL axis
+ * without a mean table, CHEB2_NOISY with d != 1 or n < 2, an unknown law. */
+#define NDQ_TABLE_MAX_AXES 6
+#define NDQ_AXIS_NORMAL 0       /* mean[c][j] + std[c][j] * N(0,1)            (GeneratorND, Generator1D '*-noisy') */
+#define NDQ_AXIS_CHEB2_NOISY 1  /* Generator1D 'chebyshev2-noisy'             (d == 1 only)                        */
+typedef struct ndq_table_sampler_desc {
+  int d;                               /* 1..6 axes; ij-meshgrid, last axis fastest */
+  int n[NDQ_TABLE_MAX_AXES];           /* nodes per axis */
+  int law[NDQ_TABLE_MAX_AXES];
+  int abs_value;                       /* GeneratorND(abs_value=True): |.| after the jitter */
+  const float* mean[NDQ_TABLE_MAX_AXES]; /* device, n[c] node positions (NORMAL) */
+  const float* std[NDQ_TABLE_MAX_AXES];  /* device, n[c] per-node widths; NULL: exact nodes */
+  float lo[NDQ_TABLE_MAX_AXES], hi[NDQ_TABLE_MAX_AXES]; /* CHEB2_NOISY: the interval */
+} ndq_table_sampler_desc;
+int ndq_sample_table(const ndq_table_sampler_desc* desc, unsigned long long seed, unsigned long long draw,
+                     unsigned stream_id, float* coords /* [d][ldc] */, int ldc, void* stream);
+
 /* Launcher exported by a generated single-network fused closure kernel (codegen.py: fused_source). */
 typedef int (*ndq_fused_launch_fn)(const float* coords, int ldc, int n, const float* params, float* partials,
                                    float* loss_partials, float* funcs, float* resid, int ldj, float seed, int train,

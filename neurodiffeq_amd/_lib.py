@@ -29,6 +29,17 @@ class SamplerDesc(ctypes.Structure):
                 ("hi", ctypes.c_float * 3), ("noise_std", ctypes.c_float * 3), ("radial", ctypes.c_int)]
 
 
+NDQ_TABLE_MAX_AXES = 6
+NDQ_AXIS_NORMAL, NDQ_AXIS_CHEB2_NOISY = 0, 1
+
+
+class TableSamplerDesc(ctypes.Structure):
+    """ndq_table_sampler_desc of include/ndq.h"""
+    _fields_ = [("d", ctypes.c_int), ("n", ctypes.c_int * 6), ("law", ctypes.c_int * 6), ("abs_value", ctypes.c_int),
+                ("mean", ctypes.c_void_p * 6), ("std", ctypes.c_void_p * 6), ("lo", ctypes.c_float * 6),
+                ("hi", ctypes.c_float * 6)]
+
+
 FUSED_LAUNCH_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                    ctypes.c_float, ctypes.c_int, ctypes.c_void_p)
@@ -99,6 +110,8 @@ def lib():
     L.ndq_fused_fit_run.argtypes = [ctypes.POINTER(FusedFit), ci, vp, ci, ci, ci, ci, vp]
     L.ndq_mlp_register.argtypes = [vp]
     L.ndq_sample.argtypes = [ctypes.POINTER(SamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci, vp]
+    L.ndq_sample_table.argtypes = [ctypes.POINTER(TableSamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci,
+                                   vp]
     L.ndq_oneshot_create.argtypes = [ci, ci, ci, ctypes.POINTER(vp), ctypes.c_char_p]
     L.ndq_oneshot_connect.argtypes = [vp, ctypes.c_char_p]
     L.ndq_oneshot_allreduce.argtypes = [vp, vp, ctypes.c_size_t, ci, ci, vp, vp]
@@ -106,8 +119,9 @@ def lib():
     L.ndq_oneshot_destroy.argtypes = [vp]
     for name in ("ndq_mlp_supported", "ndq_mlp_num_streams", "ndq_mlp_num_params", "ndq_mlp_bwd_blocks",
                  "ndq_mlp_jet_fwd", "ndq_mlp_jet_bwd", "ndq_reduce_partials", "ndq_adam_step", "ndq_reduce_grad_loss",
-                 "ndq_epoch_tail", "ndq_fused_step_run", "ndq_sample", "ndq_mlp_register", "ndq_fused_multi_step_run",
-                 "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect", "ndq_oneshot_allreduce", "ndq_oneshot_status",
+                 "ndq_epoch_tail", "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_mlp_register",
+                 "ndq_fused_multi_step_run", "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect",
+                 "ndq_oneshot_allreduce", "ndq_oneshot_status",
                  "ndq_oneshot_destroy"):
         getattr(L, name).restype = ci
     _LIB = L
@@ -154,8 +168,9 @@ EXPORTS64 = ("ndq64_mlp_register", "ndq64_mlp_supported", "ndq64_mlp_num_streams
 
 EXPORTS = ("ndq_mlp_supported", "ndq_mlp_num_streams", "ndq_mlp_num_params", "ndq_mlp_bwd_blocks", "ndq_mlp_jet_fwd",
            "ndq_mlp_jet_bwd", "ndq_reduce_partials", "ndq_adam_step", "ndq_reduce_grad_loss", "ndq_epoch_tail",
-           "ndq_fused_step_run", "ndq_sample", "ndq_mlp_register", "ndq_fused_multi_step_run", "ndq_fused_fit_run",
-           "ndq_oneshot_create", "ndq_oneshot_connect", "ndq_oneshot_allreduce", "ndq_oneshot_status", "ndq_oneshot_destroy")
+           "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_mlp_register", "ndq_fused_multi_step_run",
+           "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect", "ndq_oneshot_allreduce", "ndq_oneshot_status",
+           "ndq_oneshot_destroy")
 
 
 def check(rc, what):

@@ -823,6 +823,11 @@ int ndq_sample(const ndq_sampler_desc* desc, unsigned long long seed, unsigned l
   return ndq::launch_sample(desc, seed, draw, stream_id, coords, ldc, (hipStream_t)stream);
 }
 
+int ndq_sample_table(const ndq_table_sampler_desc* desc, unsigned long long seed, unsigned long long draw,
+                     unsigned stream_id, float* coords, int ldc, void* stream) {
+  return ndq::launch_sample_table(desc, seed, draw, stream_id, coords, ldc, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------- one-shot all-reduce

@@ -118,4 +118,100 @@ inline int launch_sample(const ndq_sampler_desc* s, unsigned long long seed, uns
   return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------------ table sampler
+// include/ndq.h: ndq_sample_table.  The node positions / jitter widths of every axis come from small device tables the
+// host built from the wrapped generator's own tensors (GeneratorND: generators.py:419-569, any method per axis, `cut`,
+// `abs_value`; Generator1D 'log-spaced[-noisy]', 'chebyshev*'), so up to six axes and any spacing cost the same kernel.
+struct TableArgs {
+  ndq_table_sampler_desc s;
+  unsigned k0, k1, c1, c2, c3;
+  float* coords;
+  int ldc, total, noisy;      // noisy == 0: no axis has a width table or a random law -- no Philox block is computed
+};
+
+// two Box-Muller pairs of one Philox block, three of the four normals: the words of NDQ_SAMPLE_GRID, in its order
+__device__ __forceinline__ void normals3(const U4& r, float& z0, float& z1, float& z2) {
+  const float r0 = sqrtf(-2.0f * __logf(u01_open(r.x))), t0 = 6.283185307179586f * u01(r.y);
+  const float r1 = sqrtf(-2.0f * __logf(u01_open(r.z))), t1 = 6.283185307179586f * u01(r.w);
+  z0 = r0 * __cosf(t0); z1 = r0 * __sinf(t0); z2 = r1 * __cosf(t1);
+}
+
+// One thread per point; every loop over the axes is unrolled to NDQ_TABLE_MAX_AXES with `c < d` guards so that n / idx /
+// z stay in registers (no runtime-indexed private array, no scratch).  Stores: consecutive lanes -> consecutive floats
+// of each SoA row.  Table reads: axis c repeats an entry over prod(n[c+1..]) consecutive points -- L1/L2 hits; in 1-D the
+// table is streamed once, coalesced.
+__global__ void __launch_bounds__(256) sample_table_kernel(TableArgs a) {
+  const unsigned iu = blockIdx.x * 256u + threadIdx.x;      // (unsigned: the last workgroup of a 2^31 - 1 point draw)
+  if (iu >= (unsigned)a.total) return;
+  const int i = (int)iu;
+  const ndq_table_sampler_desc& s = a.s;
+  // (fill_table_args admits CHEB2_NOISY on axis 0 of a one-axis descriptor only, so law[0] decides for the whole draw)
+  if (s.law[0] == NDQ_AXIS_CHEB2_NOISY) {                   // generators.py:32-34 (_chebyshev_second_noisy); d == 1
+    const U4 r = philox4x32_10(U4{(unsigned)i, a.c1, a.c2, a.c3}, a.k0, a.k1);
+    const float t = ((float)i + (2.0f * u01(r.x) - 1.0f)) / (float)(s.n[0] - 1) * 3.14159265358979f;
+    const float lo = s.lo[0], hi = s.hi[0];
+    a.coords[i] = ((lo + hi) + (hi - lo) * cosf(t)) / 2.0f;
+    return;
+  }
+  float z[NDQ_TABLE_MAX_AXES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (a.noisy) {
+    normals3(philox4x32_10(U4{(unsigned)i, a.c1, a.c2, a.c3}, a.k0, a.k1), z[0], z[1], z[2]);
+    // axes 3..5: a second block whose counter word 0 has the top bit set (total <= 2^31 - 1: no point owns that word)
+    if (s.d > 3) normals3(philox4x32_10(U4{(unsigned)i | 0x80000000u, a.c1, a.c2, a.c3}, a.k0, a.k1), z[3], z[4], z[5]);
+  }
+  unsigned rem = (unsigned)i;
+  int idx[NDQ_TABLE_MAX_AXES] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int c = NDQ_TABLE_MAX_AXES - 1; c >= 0; --c)
+    if (c < s.d) { const unsigned n = (unsigned)s.n[c]; idx[c] = (int)(rem % n); rem /= n; }
+#pragma unroll
+  for (int c = 0; c < NDQ_TABLE_MAX_AXES; ++c)
+    if (c < s.d) {
+      float v = s.mean[c][idx[c]];
+      if (s.std[c]) {
+        const float w = s.std[c][idx[c]];
+        if (w != 0.0f) v = fmaf(w, z[c], v);
+      }
+      if (s.abs_value) v = fabsf(v);
+      a.coords[(size_t)c * a.ldc + i] = v;
+    }
+}
+
+// validated launch arguments of one table draw; returns 0 or NDQ_EINVAL (nothing is launched on NDQ_EINVAL)
+inline int fill_table_args(TableArgs& a, const ndq_table_sampler_desc* s, unsigned long long seed, unsigned long long draw,
+                           unsigned stream_id, float* coords, int ldc) {
+  if (!s || !coords || s->d < 1 || s->d > NDQ_TABLE_MAX_AXES) return NDQ_EINVAL;
+  long long total = 1;
+  int noisy = 0;
+  for (int c = 0; c < s->d; ++c) {
+    if (s->n[c] < 1) return NDQ_EINVAL;
+    total *= s->n[c];
+    if (total > 0x7fffffffLL) return NDQ_EINVAL;
+    if (s->law[c] == NDQ_AXIS_NORMAL) {
+      if (!s->mean[c]) return NDQ_EINVAL;
+      noisy |= s->std[c] != nullptr;
+    } else if (s->law[c] == NDQ_AXIS_CHEB2_NOISY) {
+      if (s->d != 1 || s->n[c] < 2) return NDQ_EINVAL;
+      noisy = 1;
+    } else {
+      return NDQ_EINVAL;
+    }
+  }
+  if (ldc < total) return NDQ_EINVAL;
+  a.s = *s;
+  a.k0 = (unsigned)seed; a.k1 = (unsigned)(seed >> 32);
+  a.c1 = (unsigned)draw; a.c2 = (unsigned)(draw >> 32); a.c3 = stream_id;
+  a.coords = coords; a.ldc = ldc; a.total = (int)total; a.noisy = noisy;
+  return 0;
+}
+
+inline int launch_sample_table(const ndq_table_sampler_desc* s, unsigned long long seed, unsigned long long draw,
+                               unsigned stream_id, float* coords, int ldc, hipStream_t stream) {
+  TableArgs a;
+  const int rc = fill_table_args(a, s, seed, draw, stream_id, coords, ldc);
+  if (rc) return rc;
+  hipLaunchKernelGGL(sample_table_kernel, dim3(((unsigned)a.total + 255u) / 256u), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
 }  // namespace ndq

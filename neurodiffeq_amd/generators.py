@@ -64,6 +64,9 @@ def _rows_inplace(z, scale, shift):
 #: what a callback can change between epochs with effect -- the grid tensors, the noise widths, the getter itself.  (t_min / t_max /
 #: grid are consumed by __init__: changing them later has no effect in the reference either.)
 _LIVE = ("getter", "get_r", "examples", "grid_x", "grid_y", "grid_z", "noise_std", "noise_xstd", "noise_ystd", "size", "shape", "method")
+#: the same for the generators DeviceGenerator draws from tables (GeneratorND, the node-table laws of Generator1D); a tuple of its
+#: own: _LIVE also feeds the bulk-draw stamp of the other generators
+_LIVE_TABLE = ("grid_r", "grid_std", "getter", "examples", "noise_std", "size", "method")
 
 
 def live_stamp(gen, names=_LIVE):
@@ -483,6 +486,8 @@ class GeneratorND(BaseGenerator):
                 raise ValueError(f"Unknown method: {method}")
             axes.append(x[cut[i][0]:cut[i][1]])
             stds.append(sd[cut[i][0]:cut[i][1]])
+        # per-axis nodes / widths (after `cut`) the meshgrids are built from, and the fold: read by table_spec only
+        self.axis_r, self.axis_std, self.abs_value = axes, stds, bool(abs_value)
         self.grid_r = [m.flatten() for m in torch.meshgrid(*axes, indexing="ij")]
         self.grid_std = [m.flatten() for m in torch.meshgrid(*stds, indexing="ij")]
         if not noisy:
@@ -709,6 +714,48 @@ class ResidentBatchGenerator(BaseGenerator):
         return views
 
 
+class TableSpec:
+    """Host-side description of a table draw (``ndq_table_sampler_desc`` minus the device pointers): per axis the number of
+    nodes, the law, the fp32 node table (None for 'chebyshev2-noisy') and the fp32 width table (None: exact nodes)."""
+
+    def __init__(self, n, law, mean, std, lo, hi, abs_value):
+        self.n, self.law, self.mean, self.std, self.lo, self.hi, self.abs_value = n, law, mean, std, lo, hi, bool(abs_value)
+        self.d = len(n)
+
+
+_f32 = lambda t: np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+_TABLE_1D = ("log-spaced", "log-spaced-noisy", "chebyshev", "chebyshev1", "chebyshev2")
+
+
+def table_spec(g):
+    """:class:`TableSpec` of a generator the table sampler (``ndq_sample_table``) can draw: ``GeneratorND`` (every method,
+    ``cut``, ``noisy`` or not, ``abs_value``, up to six axes) and the node-table laws of ``Generator1D``.  The tables are the
+    tensors the generator built for itself, so exact nodes are the reference's own numbers.  ``ValueError`` for everything
+    else: 'latin-hypercube' (a permutation: index sampling stays on the host), the wrapper generators, and a ``GeneratorND``
+    whose ``grid_r`` / ``grid_std`` -- what its own getter draws from -- are no longer the meshgrids of its per-axis tensors
+    (replaced or edited after construction: the tables would draw another law than the host getter)."""
+    from . import _lib
+    normal, cheb2n = _lib.NDQ_AXIS_NORMAL, _lib.NDQ_AXIS_CHEB2_NOISY
+    if type(g) is GeneratorND and 1 <= len(g.axis_r) <= _lib.NDQ_TABLE_MAX_AXES:
+        d = len(g.axis_r)
+        mean = [_f32(x) for x in g.axis_r]
+        std = [_f32(x) for x in g.axis_std] if g.noisy else [None] * d
+        n = [len(m) for m in mean]
+        idx = np.unravel_index(np.arange(int(np.prod(n))), n)
+        for what, tables, grids in (("grid_r", mean, g.grid_r), ("grid_std", std, g.grid_std if g.noisy else [None] * d)):
+            if len(grids) != d or any(t is not None and not np.array_equal(t[idx[c]], _f32(grids[c])) for c, t in enumerate(tables)):
+                raise ValueError(f"{what} of {g!r} was changed after construction: it is not the meshgrid of the per-axis tables")
+        # (the reference folds inside the noisy getter only: noisy=False hands out the nodes as they are)
+        return TableSpec(n, [normal] * d, mean, std, [0.0] * d, [0.0] * d, g.noisy and g.abs_value)
+    if type(g) is Generator1D and g.method in _TABLE_1D:
+        mean = _f32(g.examples)
+        std = np.full(len(mean), g.noise_std, dtype=np.float32) if g.method.endswith("-noisy") else None
+        return TableSpec([len(mean)], [normal], [mean], [std], [0.0], [0.0], False)
+    if type(g) is Generator1D and g.method == "chebyshev2-noisy":
+        return TableSpec([int(g.size)], [cheb2n], [None], [None], [float(g.t_min)], [float(g.t_max)], False)
+    raise ValueError(f"the table sampler cannot draw {g!r} on the device")
+
+
 # (N, 1) view lists handed out by DeviceGenerators -> the generator (engine.fast_train_epoch asks for a prefetch)
 _DEVICE_SOURCES = {}
 
@@ -731,7 +778,11 @@ class DeviceGenerator(BaseGenerator):
     points, yet they are NOT the numbers the reference's host generator would produce, hence opt-in.
 
     Supported: ``Generator1D`` ('uniform', 'equally-spaced', 'equally-spaced-noisy'), ``Generator2D`` / ``Generator3D``
-    ('equally-spaced', 'equally-spaced-noisy'), ``GeneratorSpherical`` (both radial laws).  ``get_examples`` enqueues
+    ('equally-spaced', 'equally-spaced-noisy'), ``GeneratorSpherical`` (both radial laws) through ``ndq_sample``; and, from
+    per-axis node / width tables uploaded once (:func:`table_spec`, ``ndq_sample_table``): ``GeneratorND`` (1..6 axes, every
+    method, ``cut``, ``noisy`` or not, ``abs_value``) and ``Generator1D`` 'log-spaced', 'log-spaced-noisy', 'chebyshev' /
+    'chebyshev1', 'chebyshev2', 'chebyshev2-noisy' (no ``prefetch`` for these).  Not drawn on the device: 'latin-hypercube' (a
+    permutation) and the wrapper generators.  ``get_examples`` enqueues
     one kernel on the current stream and returns ``(N, 1)`` views of ONE resident SoA block which the fused engine
     reads in place; the block is overwritten by the next draw (stream-ordered, so the previous step has consumed it).
     (Drawing the next batch on a side stream while the current one trains was tried: the event waits between the two
@@ -753,10 +804,21 @@ class DeviceGenerator(BaseGenerator):
         self.seed = int(torch.initial_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
         self.stream_id = int(os.environ.get("RANK", "0")) if stream_id is None else int(stream_id)
         self.draw = 0
-        self.desc = self.describe(generator)
+        self.table = None            # the TableSpec when the batch is drawn by ndq_sample_table (second route), else None
+        try:
+            self.desc = self.describe(generator)
+            names = _LIVE
+        except ValueError:
+            spec = table_spec(generator)         # (ValueError: neither sampler draws this generator)
+            if prefetch:
+                raise ValueError(f"prefetch=True is not available for {generator!r}: the epoch tail's prefetch draws "
+                                 "ndq_sampler_desc laws only, and this generator is drawn from tables")
+            self._set_table(spec)
+            self.size = int(np.prod(spec.n))     # (GeneratorND: `cut` shortens the draw, `size` stays the product of `grid`)
+            names = _LIVE_TABLE
         # the descriptor froze what the wrapped generator draws from; the reference reads it at every draw (generators.py:107-416),
         # so a callback that changes a noise width / replaces a grid tensor or the getter has to be seen: live_stamp per draw
-        self._live_names = tuple(n for n in _LIVE if n in vars(generator))
+        self._live_names = tuple(n for n in names if n in vars(generator))
         self._restamp()
         self._on_host = False
         self._L = _lib.lib()
@@ -808,6 +870,26 @@ class DeviceGenerator(BaseGenerator):
             raise ValueError(f"DeviceGenerator cannot draw {g!r} on the device")
         return d
 
+    def _set_table(self, spec):
+        """Descriptor of the table route: every node / width table of ``spec`` in ONE device buffer (one upload, kept alive by
+        this generator), the descriptor's pointers into it."""
+        from . import _lib
+        d = _lib.TableSamplerDesc()
+        d.d, d.abs_value = spec.d, int(spec.abs_value)
+        parts, at, where = [], 0, {}
+        for kind, tables in (("mean", spec.mean), ("std", spec.std)):
+            for c, t in enumerate(tables):
+                if t is not None:
+                    where[kind, c] = at
+                    parts.append(np.pad(t, (0, -len(t) % 4)))      # every table starts 16-byte aligned
+                    at += len(parts[-1])
+        buf = torch.from_numpy(np.concatenate(parts) if parts else np.zeros(4, np.float32)).to(self.device)
+        for c in range(spec.d):
+            d.n[c], d.law[c], d.lo[c], d.hi[c] = spec.n[c], spec.law[c], spec.lo[c], spec.hi[c]
+            d.mean[c] = buf.data_ptr() + 4 * where["mean", c] if ("mean", c) in where else None
+            d.std[c] = buf.data_ptr() + 4 * where["std", c] if ("std", c) in where else None
+        self.table, self._table_buf, self.desc = spec, buf, d
+
     def get_examples(self):
         if torch._C._len_torch_function_stack():          # a global default-device mode: see engine.library_code
             with torch._C.DisableTorchFunction():
@@ -824,14 +906,21 @@ class DeviceGenerator(BaseGenerator):
         d = vars(g)
         # the per-draw form of the same stamp: object identity of every live attribute + the version counters of the tensors
         self._quick = tuple((n, d.get(n)) for n in self._live_names)
-        self._quick_t = tuple((v, v._version) for _, v in self._quick if isinstance(v, torch.Tensor))
+        tensors = [v for _, v in self._quick]
+        # (table route: GeneratorND keeps its tensors in lists, and ``grid_std[0] = ...`` keeps the list -- its elements as well)
+        self._quick_l = tuple((v, tuple(v)) for v in tensors if isinstance(v, (list, tuple))) if self.table is not None else ()
+        tensors += [e for _, elements in self._quick_l for e in elements]
+        self._quick_t = tuple((v, v._version) for v in tensors if isinstance(v, torch.Tensor))
         self._quick_f = type(g).get_examples
 
-    def _unchanged(self):
+    def _unchanged(self, quick=None):
         g = self.generator
         d = g.__dict__
-        for n, v in self._quick:
+        for n, v in (self._quick if quick is None else quick):
             if d.get(n) is not v:
+                return False
+        for v, elements in self._quick_l:
+            if len(v) != len(elements) or any(x is not y for x, y in zip(v, elements)):
                 return False
         for t, ver in self._quick_t:
             if t._version != ver:
@@ -843,6 +932,8 @@ class DeviceGenerator(BaseGenerator):
         tensors replaced / edited in place, another getter, another size): the wrapped generator's own host draw from now on,
         copied into the resident block -- what the reference would train on."""
         g = self.generator
+        if self.table is not None:
+            return self._table_changed()
         try:
             new = self.describe(g)
             same_shape = new.kind == self.desc.kind and new.d == self.desc.d and list(new.n) == list(self.desc.n) and g.size == self.size
@@ -855,10 +946,30 @@ class DeviceGenerator(BaseGenerator):
             self.desc = new
             self.prefetched = None              # (a batch drawn ahead by a tail kernel used the old widths)
         else:
-            self._on_host, self.prefetch, self.prefetched = True, False, None
-            warnings.warn("neurodiffeq_amd: a generator wrapped by DeviceGenerator was changed in a way the device sampler cannot "
-                          "follow (grid tensors / getter / size); its own host draw is used from now on (the reference's numbers, "
-                          "uploaded every epoch).", RuntimeWarning)
+            self._to_host()
+        self._restamp()
+
+    def _to_host(self):
+        self._on_host, self.prefetch, self.prefetched = True, False, None
+        warnings.warn("neurodiffeq_amd: a generator wrapped by DeviceGenerator was changed in a way the device sampler cannot "
+                      "follow (grid tensors / getter / size); its own host draw is used from now on (the reference's numbers, "
+                      "uploaded every epoch).", RuntimeWarning)
+
+    def _table_changed(self):
+        """Table route: a new ``noise_std`` number on a Generator1D rebuilds the width table; anything else (node or width tensors
+        replaced / edited, another getter, size or method): the wrapped generator's own host draw from now on."""
+        g = self.generator
+        rest_same = self._unchanged(tuple(p for p in self._quick if p[0] != "noise_std"))
+        spec = None
+        if rest_same and type(g) is Generator1D and isinstance(g.noise_std, (int, float)):
+            try:
+                spec = table_spec(g)
+            except ValueError:
+                spec = None
+        if spec is not None and (spec.n, spec.law) == (self.table.n, self.table.law):
+            self._set_table(spec)
+        else:
+            self._to_host()
         self._restamp()
 
     def _host_examples(self):
@@ -886,11 +997,11 @@ class DeviceGenerator(BaseGenerator):
             self.prefetched = None
         else:
             stream = ctypes.c_void_p(_raw_stream(self.device.index))       # (torch.cuda.current_stream(): ~10 us per call)
-            rc = self._L.ndq_sample(ctypes.byref(self.desc), self.seed, self.draw, self.stream_id, block.data_ptr(),
-                                    block.shape[1], stream)
+            sample = self._L.ndq_sample if self.table is None else self._L.ndq_sample_table
+            rc = sample(ctypes.byref(self.desc), self.seed, self.draw, self.stream_id, block.data_ptr(), block.shape[1], stream)
             if rc != 0:
                 from . import _lib
-                raise _lib.NdqError(f"ndq_sample failed with code {rc}")
+                raise _lib.NdqError(f"{sample.__name__} failed with code {rc}")
             self.launches += 1
         slot = (self.draw & 1) if self.prefetch else 0
         if self.dtype != torch.float32:
