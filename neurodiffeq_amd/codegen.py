@@ -165,93 +165,23 @@ _UN_ADJ = {
 }
 
 
-def _tv_launcher(args_t, fill, kern_tv, lds_train, lds_eval, threads="CFG::BWD_THREADS", kern_loop=None, lds_loop=None):
-    """Host launcher of the train + validation closure kernel (csrc/ndq_mlp.h: fused_*_closure_tv_kernel), emitted into
-    the anonymous namespace of every generated closure module: workgroups [0, blocks(n)) run the training closure on the
-    training batch, the next blocks(vn) the forward-only closure on the validation batch; n = 0 / vn = 0 drops a half."""
-    return f"""
-int launch_tv(const float* coords, int ldc, int n, const float* const* params, float* const* partials, float* loss_partials,
-              float seed, const float* vcoords, int vldc, int vn, float* vloss_partials, const void* pull, void* stream) {{
-  if (!params || n < 0 || vn < 0 || (n == 0 && vn == 0)) return -2;
-  if (n > 0 && (!coords || !partials || !loss_partials || ldc < n)) return -2;
-  if (vn > 0 && (!vcoords || !vloss_partials || vldc < vn)) return -2;
-  {args_t} t{{}}, v{{}};
-  {{
-    {args_t}& a = t;
-    a.coords = coords; a.loss_partials = loss_partials; a.n = n; a.ldc = ldc; a.ldj = ldc; a.seed = seed;
-    a.theta = g_theta; a.theta_partials = g_theta_partials;
-    {fill}
-  }}
-  {{
-    {args_t}& a = v;
-    float* const* partials = nullptr;
-    a.coords = vcoords; a.loss_partials = vloss_partials; a.n = vn; a.ldc = vldc; a.ldj = vldc; a.seed = 0.f;
-    a.theta = g_theta;
-    {fill}
-  }}
-  // a training epoch on its own is the plain training kernel (the same device code as the training half of the combined
-  // kernel -- engine.verify_fused compares the two bit for bit -- without the second body's registers: C2 -1 us, C3 -13 us)
-  static const bool always_tv = getenv("NDQ_TV_ALWAYS") != nullptr;        // measurement knob
-  if (vn == 0 && !pull && !always_tv)
-    return launch(coords, ldc, n, params, partials, loss_partials, nullptr, nullptr, ldc, seed, 1, stream);
-  const int tb = n > 0 ? fused_blocks(n) : 0, vb = vn > 0 ? fused_blocks(vn) : 0;
-  static bool attr = false;
-  if (!attr) {{
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&{kern_tv}),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int){lds_train});
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }}
-  ndq::PullArgs pa{{}};        // pull prologue (csrc/ndq_tail.h): the launch finishes the previous epoch itself
-  if (pull) {{
-    if (!ndq::pull_supported<CFG>()) return -2;
-    pa = *static_cast<const ndq::PullArgs*>(pull);
-  }}
-  hipLaunchKernelGGL(({kern_tv}), dim3(tb + vb), dim3({threads}), tb > 0 ? {lds_train} : {lds_eval},
-                     static_cast<hipStream_t>(stream), t, v, tb, pa);
-  return (int)hipGetLastError();
-}}""" + (f"""
-// loop mode (csrc/ndq_tail.h: LoopArgs): ONE workgroup runs a run of fit()'s launches back to back, state in LDS
-int launch_loop(const float* coords, int ldc, int n, float seed, const float* vcoords, int vldc, int vn, const void* loop,
-                void* stream) {{
-  if (!loop || !ndq::pull_supported<CFG>() || n < 0 || vn < 0 || (n > 0 && (!coords || ldc < n || fused_blocks(n) != 1)) ||
-      (vn > 0 && (!vcoords || vldc < vn || fused_blocks(vn) != 1)))
-    return -2;
-  {args_t} t{{}}, v{{}};
-  t.coords = coords; t.n = n; t.ldc = ldc; t.ldj = ldc; t.seed = seed; t.theta = g_theta;
-  v.coords = vcoords; v.n = vn; v.ldc = vldc; v.ldj = vldc; v.seed = 0.f; v.theta = g_theta;
-  static bool attr = false;
-  if (!attr) {{
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&{kern_loop}),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int){lds_loop});
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }}
-  hipLaunchKernelGGL(({kern_loop}), dim3(1), dim3({threads}), {lds_loop}, static_cast<hipStream_t>(stream), t, v,
-                     *static_cast<const ndq::LoopArgs*>(loop));
-  return (int)hipGetLastError();
-}}
-int loop_ok() {{ return ndq::pull_supported<CFG>() && {lds_loop} <= 160 * 1024 ? 1 : 0; }}
-""" if kern_loop else """
-int launch_loop(const float*, int, int, float, const float*, int, int, const void*, void*) { return -2; }
-int loop_ok() { return 0; }
-""")
-
-
-# the ndq_fused_launch_tv_fn of include/ndq.h
-_TV_EXPORT = """
-extern "C" int ndq_fused_launch_tv(const float* coords, int ldc, int n, const float* const* params, float* const* partials,
-                                   float* loss_partials, float seed, const float* vcoords, int vldc, int vn,
-                                   float* vloss_partials, const void* pull, void* stream) {
-  return launch_tv(coords, ldc, n, params, partials, loss_partials, seed, vcoords, vldc, vn, vloss_partials, pull, stream);
-}
-extern "C" int ndq_fused_pull_ok() { return ndq::pull_supported<CFG>() ? 1 : 0; }
-// the ndq_fused_launch_loop_fn of include/ndq.h
-extern "C" int ndq_fused_launch_loop(const float* coords, int ldc, int n, float seed, const float* vcoords, int vldc, int vn,
-                                     const void* loop, void* stream) {
-  return launch_loop(coords, ldc, n, seed, vcoords, vldc, vn, loop, stream);
-}
-extern "C" int ndq_fused_loop_ok() { return loop_ok(); }
+def _closure_host(K, threads, points, slots, kern, kern_tv, lds, kern_loop=None, lds_loop=None):
+    """Tail of a generated closure module: the traits struct ``Closure`` (what differs between the closure kernels; the
+    contract is the file comment of csrc/ndq_closure_host.h), then that header -- the launchers and every ndq_fused_* export.
+    kern(train) / lds(train): C++ text of the plain kernel and of its LDS bytes; kern_loop=None: no loop-mode kernel."""
+    return f"""struct Closure {{
+  using Cfg = CFG;
+  using Pw = PW;
+  using Args = ndq::{'FusedArgs' if K == 1 else 'FusedMultiArgs'};
+  static constexpr int K = {K}, THREADS = {threads}, POINTS = {points}, SLOTS = {slots};
+  static constexpr auto train = &{kern('true')};
+  static constexpr auto eval = &{kern('false')};
+  static constexpr auto tv = &{kern_tv};
+  static constexpr auto loop = {'&' + kern_loop if kern_loop else 'nullptr'};
+  static constexpr size_t LDS_TRAIN = {lds('true')}, LDS_EVAL = {lds('false')}, LDS_LOOP = {lds_loop or 0};
+}};
+}}  // namespace
+#include "ndq_closure_host.h"
 """
 
 
@@ -575,14 +505,7 @@ NDQ_PW_INLINE float ndq_pw_loss(const float* r) {{ return {term}; }}
         # workgroup shape: waves x tiles per round (multi-network closure: K x G waves, G tile slots -- csrc/ndq_mlp.h)
         threads = "CFG::BWD_THREADS" if K == 1 else f"ndq::multi_threads<{K}>()"
         tiles_per_block = "CFG::BWD_THREADS / 64" if K == 1 else f"ndq::multi_group<{K}>()"
-        if K == 1:
-            args_t = "ndq::FusedArgs"
-            fill = "a.params = params[0]; a.partials = partials ? partials[0] : nullptr;"
-            kern_tv = "ndq::fused_closure_tv_kernel<CFG, PW>"
-        else:
-            args_t = "ndq::FusedMultiArgs"
-            fill = f"for (int k = 0; k < {K}; ++k) {{ a.params[k] = params[k]; a.partials[k] = partials ? partials[k] : nullptr; }}"
-            kern_tv = f"ndq::fused_multi_closure_tv_kernel<CFG, {K}, PW>"
+        kern_tv = "ndq::fused_closure_tv_kernel<CFG, PW>" if K == 1 else f"ndq::fused_multi_closure_tv_kernel<CFG, {K}, PW>"
         if f64:
             kern_loop = lds_loop = None          # (loop / pull mode: fp32 only, csrc/ndq_tail.h)
         elif K == 1:
@@ -591,13 +514,12 @@ NDQ_PW_INLINE float ndq_pw_loss(const float* r) {{ return {term}; }}
             kern_loop, lds_loop = f"ndq::fused_multi_closure_loop_kernel<CFG, {K}, PW>", f"(ndq::fused_multi_loop_lds_bytes<CFG, {K}>())"
         else:
             kern_loop = lds_loop = None
-        tv = _tv_launcher(args_t, fill, kern_tv, lds('true'), lds('false'), threads, kern_loop, lds_loop)
+        host = _closure_host(K, threads, 16, tiles_per_block, kern, kern_tv, lds, kern_loop, lds_loop)
         # hidden-layer weight gradients from the bf16x3 planes through transposing LDS reads (csrc/ndq_mlp.h Cfg::WG_TR;
         # shapes it does not cover, or whose K images would not fit the LDS, ignore the switch)
         wg_tr = f"#ifndef NDQ_WG_TR\n#define NDQ_WG_TR 1\n#endif\n#define NDQ_WG_TR_K {K}\n" + CLOSURE_PRODUCTS
         return f"""// GENERATED by neurodiffeq_amd/codegen.py -- single-launch closure kernel (forward streams + pointwise stage +
 // reverse pass) of one PDE system with {K} network(s), gfx950.
-#include <cstdlib>
 {wg_tr}#include "{header}"
 #define NDQ_PW_INLINE __device__ __forceinline__
 #ifndef NDQ_MAX_BLOCKS
@@ -605,7 +527,7 @@ NDQ_PW_INLINE float ndq_pw_loss(const float* r) {{ return {term}; }}
 #endif
 {self.point_fn_source()}
 namespace {{
-using CFG = ndq::Cfg<{desc.d}, {desc.first}, {desc.mask2}u, {(desc.hidden + 15) // 16}, {desc.layers}, {desc.act}, 1, {desc.lap}, {desc.skip}, {desc.mask3}u, {desc.actp}, {desc.hidden if (desc.hidden % 16 or desc.widths) else 0}, {desc.widths}u, {desc.mono}u{_m4_arg(desc)}>;
+using CFG = {mlp_cfg(desc, 1)};
 struct PW {{
   // ND per-point data columns (rows D .. D + ND of the coordinate block), NT trainable scalars of the equations
   static constexpr int NEQ = {neq}, NF = {nf}, NR = {self.n_r}, ND = {self.n_data}, NT = {self.n_theta};
@@ -626,85 +548,7 @@ struct PW {{
     for (int j = 0; j < NT; ++j) gth[j] = g[{len(self.symbols)} + j];
   }}
 }};
-constexpr int kWaves = {tiles_per_block};        // tiles a workgroup handles per round
-int fused_blocks(int n) {{
-  const int tiles = (n + 15) / 16;
-  int b = (tiles + kWaves - 1) / kWaves;
-  return b > NDQ_MAX_BLOCKS ? NDQ_MAX_BLOCKS : (b < 1 ? 1 : b);
-}}
-
-// trainable scalars of the equations (PW::NT of them): values read by every launch, block sums of their adjoints written by
-// training launches -- bound by the engine before it launches (ndq_fused_bind_theta)
-const float* g_theta = nullptr;
-float* g_theta_partials = nullptr;
-
-// params / partials: host arrays of {K} device pointers (one per network)
-int launch(const float* coords, int ldc, int n, const float* const* params, float* const* partials, float* loss_partials,
-           float* funcs, float* resid, int ldj, float seed, int train, void* stream) {{
-  if (!coords || !params || !loss_partials || n <= 0 || ldc < n || (train && !partials)) return -2;
-  if (PW::NT > 0 && !g_theta) return -2;
-  {args_t} a{{}};
-  a.coords = coords; a.loss_partials = loss_partials;
-  {fill}
-  a.funcs = funcs; a.resid = resid; a.n = n; a.ldc = ldc; a.ldj = ldj; a.seed = seed;
-  a.theta = g_theta; a.theta_partials = train ? g_theta_partials : nullptr;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  static bool attr = false;
-  if (!attr) {{
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&{kern('true')}),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int){lds('true')});
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&{kern('false')}),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int){lds('false')});
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }}
-  if (train)
-    hipLaunchKernelGGL(({kern('true')}), dim3(fused_blocks(n)), dim3({threads}), {lds('true')}, s, a);
-  else
-    hipLaunchKernelGGL(({kern('false')}), dim3(fused_blocks(n)), dim3({threads}), {lds('false')}, s, a);
-  return (int)hipGetLastError();
-}}
-{tv}
-}}  // namespace
-
-extern "C" int ndq_fused_blocks(int n) {{ return fused_blocks(n); }}
-extern "C" int ndq_fused_num_params() {{ return CFG::P; }}
-extern "C" int ndq_fused_num_theta() {{ return PW::NT; }}
-extern "C" void ndq_fused_bind_theta(const float* theta, float* theta_partials) {{ g_theta = theta; g_theta_partials = theta_partials; }}
-extern "C" int ndq_fused_num_nets() {{ return {K}; }}
-extern "C" int ndq_fused_threads() {{ return {threads}; }}
-extern "C" unsigned long ndq_fused_lds_bytes() {{ return (unsigned long){lds('true')}; }}
-
-#ifdef NDQ_PHASE_TS
-extern "C" int ndq_fused_phase_ts(unsigned long long* out) {{    // experiments: scripts/phase_ts.py
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ndq::ndq_phase_ts), sizeof(unsigned long long) * 256 * 8);
-}}
-extern "C" int ndq_fused_pull_ts(unsigned long long* out) {{    // experiments: scripts/pull_ts.py
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ndq::ndq_pull_ts), sizeof(unsigned long long) * 8);
-}}
-extern "C" int ndq_fused_tile_ts(unsigned long long* out) {{
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ndq::ndq_tile_ts), sizeof(unsigned long long) * 48);
-}}
-#endif
-
-// one network: the ndq_fused_launch_fn of include/ndq.h
-extern "C" int ndq_fused_launch(const float* coords, int ldc, int n, const float* params, float* partials,
-                                float* loss_partials, float* funcs, float* resid, int ldj, float seed, int train,
-                                void* stream) {{
-  if ({K} != 1) return -2;
-  const float* pp[1] = {{params}};
-  float* qq[1] = {{partials}};
-  return launch(coords, ldc, n, pp, partials ? qq : nullptr, loss_partials, funcs, resid, ldj, seed, train, stream);
-}}
-
-// any number of networks: params / partials are host arrays of device pointers
-extern "C" int ndq_fused_launch_multi(const float* coords, int ldc, int n, const float* const* params,
-                                      float* const* partials, float* loss_partials, float* funcs, float* resid, int ldj,
-                                      float seed, int train, void* stream) {{
-  return launch(coords, ldc, n, params, partials, loss_partials, funcs, resid, ldj, seed, train, stream);
-}}
-{_TV_EXPORT}"""
+{host}"""
 
     def _group_source(self, desc, wide=False):
         """Source of the grouped single-launch closure kernel (csrc/ndq_mlp.h: fused_group_closure_kernel): one network
@@ -733,25 +577,16 @@ extern "C" int ndq_fused_launch_multi(const float* coords, int ldc, int n, const
         kern = lambda train: f"ndq::fused_group_closure_kernel<CFG, PW, {train}>"
         lds = lambda train: f"ndq::group_lds_bytes<CFG>({train})"
         kern_tv = "ndq::fused_group_closure_tv_kernel<CFG, PW>"
-        cfg_t = (f"ndq::Cfg<{desc.d}, {desc.first}, {desc.mask2}u, {(desc.hidden + 15) // 16}, {desc.layers}, {desc.act}, "
-                 f"{desc.n_out}, {desc.lap}, {desc.skip}, {desc.mask3}u, {desc.actp}, "
-                 f"{desc.hidden if (desc.hidden % 16 or desc.widths) else 0}, {desc.widths}u, {desc.mono}u{_m4_arg(desc)}>")
-        blocks_body = """  constexpr int gp = 16 * ndq::group_tiles<CFG>();
-  const int groups = (n + gp - 1) / gp;
-  int b = (groups + kWaves - 1) / kWaves;"""
+        cfg_t, points = mlp_cfg(desc, desc.n_out), "16 * ndq::group_tiles<CFG>()"
         if wide:
             header = "ndq_wide.h"
             kern = lambda train: f"ndq::wide_closure_kernel<CFG, PW, {train}>"
             lds = lambda train: "(ndq::wide_closure_lds_bytes<CFG, PW>())"
             kern_tv = "ndq::wide_closure_tv_kernel<CFG, PW>"
-            cfg_t = wide_cfg(desc)
-            blocks_body = """  const int tiles = (n + 15) / 16;
-  int b = (tiles + kWaves - 1) / kWaves;"""
-        tv = _tv_launcher("ndq::FusedArgs", "a.params = params[0]; a.partials = partials ? partials[0] : nullptr;",
-                          kern_tv, lds('true'), lds('false'))
+            cfg_t, points = wide_cfg(desc), 16
+        host = _closure_host(1, "CFG::BWD_THREADS", points, "CFG::BWD_THREADS / 64", kern, kern_tv, lds)
         return f"""// GENERATED by neurodiffeq_amd/codegen.py -- grouped single-launch closure kernel (forward streams -> LDS exchange ->
 // per-point stage, one point per lane -> reverse pass) of one PDE system, gfx950.
-#include <cstdlib>
 {CLOSURE_PRODUCTS}#include "{header}"
 #define NDQ_PW_INLINE __device__ __forceinline__
 #ifndef NDQ_MAX_BLOCKS
@@ -781,75 +616,7 @@ struct PW {{
     for (int j = 0; j < NT; ++j) gth[j] = g[{len(self.symbols)} + j];
   }}
 }};
-constexpr int kWaves = CFG::BWD_THREADS / 64;
-int fused_blocks(int n) {{
-{blocks_body}
-  return b > NDQ_MAX_BLOCKS ? NDQ_MAX_BLOCKS : (b < 1 ? 1 : b);
-}}
-
-const float* g_theta = nullptr;          // see the tile-closure module: trainable scalars of the equations
-float* g_theta_partials = nullptr;
-
-int launch(const float* coords, int ldc, int n, const float* const* params, float* const* partials, float* loss_partials,
-           float* funcs, float* resid, int ldj, float seed, int train, void* stream) {{
-  if (!coords || !params || !loss_partials || n <= 0 || ldc < n || (train && !partials)) return -2;
-  if (PW::NT > 0 && !g_theta) return -2;
-  ndq::FusedArgs a{{}};
-  a.coords = coords; a.loss_partials = loss_partials;
-  a.params = params[0]; a.partials = partials ? partials[0] : nullptr;
-  a.funcs = funcs; a.resid = resid; a.n = n; a.ldc = ldc; a.ldj = ldj; a.seed = seed;
-  a.theta = g_theta; a.theta_partials = train ? g_theta_partials : nullptr;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  static bool attr = false;
-  if (!attr) {{
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&{kern('true')}),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int){lds('true')});
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&{kern('false')}),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int){lds('false')});
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }}
-  if (train)
-    hipLaunchKernelGGL(({kern('true')}), dim3(fused_blocks(n)), dim3(CFG::BWD_THREADS), {lds('true')}, s, a);
-  else
-    hipLaunchKernelGGL(({kern('false')}), dim3(fused_blocks(n)), dim3(CFG::BWD_THREADS), {lds('false')}, s, a);
-  return (int)hipGetLastError();
-}}
-{tv}
-}}  // namespace
-
-extern "C" int ndq_fused_blocks(int n) {{ return fused_blocks(n); }}
-extern "C" int ndq_fused_num_params() {{ return CFG::P; }}
-extern "C" int ndq_fused_num_theta() {{ return PW::NT; }}
-extern "C" void ndq_fused_bind_theta(const float* theta, float* theta_partials) {{ g_theta = theta; g_theta_partials = theta_partials; }}
-extern "C" int ndq_fused_num_nets() {{ return 1; }}
-extern "C" int ndq_fused_threads() {{ return CFG::BWD_THREADS; }}
-extern "C" unsigned long ndq_fused_lds_bytes() {{ return (unsigned long){lds('true')}; }}
-
-#ifdef NDQ_PHASE_TS
-extern "C" int ndq_fused_phase_ts(unsigned long long* out) {{    // experiments: scripts/phase_ts_group.py
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ndq::ndq_phase_ts), sizeof(unsigned long long) * 256 * 8);
-}}
-extern "C" int ndq_fused_tile_ts(unsigned long long* out) {{
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ndq::ndq_tile_ts), sizeof(unsigned long long) * 48);
-}}
-#endif
-
-extern "C" int ndq_fused_launch(const float* coords, int ldc, int n, const float* params, float* partials,
-                                float* loss_partials, float* funcs, float* resid, int ldj, float seed, int train,
-                                void* stream) {{
-  const float* pp[1] = {{params}};
-  float* qq[1] = {{partials}};
-  return launch(coords, ldc, n, pp, partials ? qq : nullptr, loss_partials, funcs, resid, ldj, seed, train, stream);
-}}
-
-extern "C" int ndq_fused_launch_multi(const float* coords, int ldc, int n, const float* const* params,
-                                      float* const* partials, float* loss_partials, float* funcs, float* resid, int ldj,
-                                      float seed, int train, void* stream) {{
-  return launch(coords, ldc, n, params, partials, loss_partials, funcs, resid, ldj, seed, train, stream);
-}}
-{_TV_EXPORT}"""
+{host}"""
 
     def _emit(self):
         nsym = max(len(self.symbols), 1)
@@ -1093,7 +860,8 @@ def _build_tag():
 
 def _header_digest():
     h = hashlib.sha1()
-    for name in ("csrc/ndq_mlp.h", "csrc/ndq_tail.h", "csrc/ndq_launch.h", "csrc/ndq_wide.h", "csrc/ndq_deep.h", "../include/ndq.h"):
+    for name in ("csrc/ndq_mlp.h", "csrc/ndq_tail.h", "csrc/ndq_launch.h", "csrc/ndq_wide.h", "csrc/ndq_deep.h", "csrc/ndq_closure_host.h",
+                 "../include/ndq.h"):
         with open(os.path.join(HERE, name), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()
@@ -1166,6 +934,13 @@ def is_wide(desc):
     return desc.hidden > 64
 
 
+def mlp_cfg(desc, n_out):
+    """The ndq::Cfg instantiation of a descriptor with ``n_out`` outputs (csrc/ndq_mlp.h: hidden layers of up to 64 units)."""
+    return (f"ndq::Cfg<{desc.d}, {desc.first}, {desc.mask2}u, {(desc.hidden + 15) // 16}, {desc.layers}, {desc.act}, {n_out}, "
+            f"{desc.lap}, {desc.skip}, {desc.mask3}u, {desc.actp}, {desc.hidden if (desc.hidden % 16 or desc.widths) else 0}, "
+            f"{desc.widths}u, {desc.mono}u{_m4_arg(desc)}>")
+
+
 def deep_cfg(desc):
     """The ndq::DeepCfg instantiation of a descriptor (2 .. 8 hidden layers of 65 .. 512 units, csrc/ndq_deep.h)."""
     return (f"ndq::DeepCfg<{desc.d}, {desc.first}, {desc.mask2}u, {desc.lap}, {desc.mask3}u, {desc.hidden}, {desc.layers}, "
@@ -1218,7 +993,7 @@ extern "C" const {record}* ndq_ext_kernels(void) {{
     return f"""// GENERATED by neurodiffeq_amd/codegen.py -- forward-stream and adjoint kernels of one FCNN shape / stream set
 {"#define NDQ_F64 1" if f64 else ""}
 #include "{header}"
-using CFG = ndq::Cfg<{desc.d}, {desc.first}, {desc.mask2}u, {(desc.hidden + 15) // 16}, {desc.layers}, {desc.act}, {desc.n_out}, {desc.lap}, {desc.skip}, {desc.mask3}u, {desc.actp}, {desc.hidden if (desc.hidden % 16 or desc.widths) else 0}, {desc.widths}u, {desc.mono}u{_m4_arg(desc)}>;
+using CFG = {mlp_cfg(desc, desc.n_out)};
 extern "C" const {record}* ndq_ext_kernels(void) {{
   static const {record} k = ndq::make_kernels<CFG>();
   return &k;

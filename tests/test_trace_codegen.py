@@ -748,6 +748,35 @@ def test_outside_numbers_that_move_become_runtime_constants_of_the_generated_ker
     assert d.n_theta == 0
 
 
+def _load_closure(so):
+    import ctypes
+    lib = ctypes.CDLL(so)
+    lib.ndq_fused_lds_bytes.restype = ctypes.c_ulong
+    return lib
+
+
+def _fused_exports(so):
+    """The ndq_fused_* names a generated closure module defines in its dynamic symbol table (ELF64, little endian)."""
+    import struct
+    with open(so, "rb") as fh:
+        elf = fh.read()
+    assert elf[:6] == b"\x7fELF\x02\x01"
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", elf, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for _, kind, _, _, offset, size, link, _, _, entsize in sections:
+        if kind != 11:                                        # SHT_DYNSYM
+            continue
+        strtab = sections[link][4]
+        for at in range(offset, offset + size, entsize):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", elf, at)
+            name = elf[strtab + st_name:elf.index(b"\0", strtab + st_name)].decode()
+            if st_shndx != 0 and name.startswith("ndq_fused_"):       # (defined here, not imported)
+                names.add(name)
+    return sorted(names)
+
+
 def test_fp64_closure_source_is_the_fp32_module_rewritten_for_double():
     """codegen.can_fuse_f64 / fused_source(f64=True): single-network systems on the plain closure kernel get the SAME generated
     module under NDQ_F64 -- types, math calls and literal suffixes rewritten, no loop / pull launcher (fp32 only) --, other
@@ -769,9 +798,52 @@ def test_fp64_closure_source_is_the_fp32_module_rewritten_for_double():
     assert src.startswith("#define NDQ_F64 1\n")
     assert not re.search(r"\bfloat\b", src) and "double" in src
     assert not re.search(r"\d\.\d+f\b", src) and "expf(" not in src and "tanhf(" not in src
-    assert "fused_closure_loop_kernel" not in src and "ndq_fused_launch_tv" in src
-    assert src != program.fused_source(descs[0])                      # (and the fp32 module is untouched by the flag)
-    assert "#define NDQ_F64" not in program.fused_source(descs[0])
+    # no loop / pull launcher: the traits of the fp64 module name no loop kernel (the fp32 ones do) ...
+    assert "fused_closure_loop_kernel" not in src and "static constexpr auto loop = nullptr;" in src
+    src32 = program.fused_source(descs[0])
+    assert "static constexpr auto loop = &ndq::fused_closure_loop_kernel<CFG, PW>;" in src32
+    # ... and the launchers live in csrc/ndq_closure_host.h, written against ndq::real: the module built from this source has
+    # the train + validation entry point and reports "no loop mode" (loading it and asking touches no GPU)
+    assert src.rstrip().endswith('#include "ndq_closure_host.h"') and "ndq_fused_" not in src
+    lib = _load_closure(codegen.build_fused(program, descs[0], f64=True))
+    assert "ndq_fused_launch_tv" in _fused_exports(lib._name)
+    assert lib.ndq_fused_loop_ok() == 0 and lib.ndq_fused_pull_ok() == 0
+    assert src != src32                                               # (and the fp32 module is untouched by the flag)
+    assert "#define NDQ_F64" not in src32
     for name in ("c1", "c4"):                                         # two networks / the grouped closure: pipeline in double
         program, descs = traced(name)
         assert not codegen.can_fuse_f64(program, descs)
+
+
+#: What the generated closure modules export and answer, per closure kernel family.  The numbers were read from the modules of
+#: the commit BEFORE the launch code moved into csrc/ndq_closure_host.h (its build of these four systems, loaded with ctypes):
+#: (system, fuse mode, networks, threads, LDS bytes, ndq_fused_blocks(n) for n in CLOSURE_HOST_N).  The name set is that
+#: commit's too: thirteen names, the same for every mode.
+CLOSURE_HOST_N = (1, 15, 16, 17, 4096, 65536, 10_000_000)
+CLOSURE_HOST_EXPORTS = sorted("ndq_fused_" + n for n in (
+    "blocks", "num_params", "num_theta", "bind_theta", "num_nets", "threads", "lds_bytes", "launch", "launch_multi", "launch_tv",
+    "pull_ok", "launch_loop", "loop_ok"))
+CLOSURE_HOST_CASES = [
+    ("c2", "tile", 1, 256, 86672, (1, 1, 1, 1, 64, 256, 256)),
+    ("c1", "multi", 2, 256, 75872, (1, 1, 1, 1, 128, 256, 256)),
+    ("c4", "group", 1, 256, 161344, (1, 1, 1, 1, 16, 256, 256)),
+    ("w16", "wide", 1, 256, 72080, (1, 1, 1, 1, 64, 256, 256)),
+]
+
+
+@pytest.mark.parametrize("name,mode,nets,threads,lds,blocks", CLOSURE_HOST_CASES, ids=[c[1] for c in CLOSURE_HOST_CASES])
+def test_closure_module_exports_and_queries_are_those_of_the_inline_launchers(name, mode, nets, threads, lds, blocks):
+    """csrc/ndq_closure_host.h behind one traits struct per mode: every kind of generated closure module compiles (build() has
+    compiled exactly these: a cache hit here), exports the same ndq_fused_* names as when each module carried its own copy of
+    the launch code, and answers the geometry queries with the same numbers."""
+    from neurodiffeq_amd import engine
+    torch.manual_seed(0)
+    cfg = configs.make(name, 8 if name.startswith("c") else None)
+    program, descs = engine.trace_system(cfg["nets"], cfg["conds"], configs.fused_equations(cfg), configs.n_coords(cfg),
+                                         compute_func_val=configs.func_val(cfg))
+    assert codegen.fuse_mode(program, descs) == mode
+    so = codegen.build_fused(program, descs[0])
+    assert _fused_exports(so) == CLOSURE_HOST_EXPORTS
+    lib = _load_closure(so)
+    assert (lib.ndq_fused_num_nets(), lib.ndq_fused_threads(), lib.ndq_fused_lds_bytes()) == (nets, threads, lds)
+    assert tuple(lib.ndq_fused_blocks(n) for n in CLOSURE_HOST_N) == blocks
