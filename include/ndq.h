@@ -177,6 +177,59 @@ typedef struct ndq_table_sampler_desc {
 int ndq_sample_table(const ndq_table_sampler_desc* desc, unsigned long long seed, unsigned long long draw,
                      unsigned stream_id, float* coords /* [d][ldc] */, int ldc, void* stream);
 
+/* Plan sampler: a composed draw -- the reference's ConcatGenerator (g1 + g2), EnsembleGenerator (g1 * g2) and MeshGenerator
+ * (g1 ^ g2) over leaf generators -- by ONE kernel, one thread per output point, no temporaries.
+ *   plan    := segments, concatenated along the points: segment s writes points [offset, offset + size) of all d rows
+ *   segment := LEAF (one leaf of d rows) | ENSEMBLE (leaves of equal size side by side: leaf l writes rows row0 ..
+ *              row0 + rows - 1) | MESH (ij-meshgrid of one-row leaves, last factor fastest)
+ *   leaf    := SIMPLE (an ndq_sampler_desc law) | TABLE (an ndq_table_sampler_desc law) | DATA (rows of `n` fixed floats in
+ *              device memory, copied bit for bit)
+ * Segment s owns leaves first .. first + count - 1; leaves are numbered in that order from 0.  Leaf l is drawn under the
+ * key seed + l * 0x9E3779B97F4A7C15 (mod 2^64) with the counter words of ndq_sample / ndq_sample_table, word 0 being the
+ * leaf-LOCAL point index: the local index of the output point in a LEAF / ENSEMBLE segment, its unravelled component in
+ * a MESH -- so leaf l's rows are what ndq_sample / ndq_sample_table write for that leaf alone under that key, composed as
+ * torch.cat / a tuple / torch.meshgrid(indexing="ij") compose them, and a mesh factor's jitter at one of its nodes is
+ * the same for every partner node.  A Philox block is computed only for a leaf with a random law or a width table.
+ * NDQ_EINVAL (nothing launched): a null pointer, d outside 1..6, n_leaves outside 1..8, n_segments outside 1..n_leaves,
+ * segments that do not own the leaves 0 .. n_leaves - 1 in order, an unknown mode or kind, a LEAF segment of count != 1, a
+ * leaf its own entry point would refuse, `rows` other than the law's d (DATA: outside 1..6, a null row, n < 1), a segment
+ * whose leaves do not cover rows 0 .. d - 1 exactly once, an ENSEMBLE leaf whose size is not the segment's, a MESH factor of
+ * more than one row or a MESH whose product of sizes is not the segment's, an offset that is not the sum of the earlier
+ * sizes, more than 2^31 - 1 points in all, ldc < points. */
+#define NDQ_PLAN_MAX_LEAVES 8
+#define NDQ_LEAF_SIMPLE 0
+#define NDQ_LEAF_TABLE 1
+#define NDQ_LEAF_DATA 2
+#define NDQ_SEG_LEAF 0
+#define NDQ_SEG_ENSEMBLE 1
+#define NDQ_SEG_MESH 2
+typedef struct ndq_plan_leaf {
+  int kind;  /* NDQ_LEAF_* */
+  int row0;  /* first output row */
+  int rows;  /* output rows (the law's d) */
+  int n;     /* DATA: number of points (other kinds: the law's own size) */
+  union {
+    ndq_sampler_desc simple;
+    ndq_table_sampler_desc table;
+    const float* data[NDQ_TABLE_MAX_AXES]; /* device, rows x n floats */
+  } u;
+} ndq_plan_leaf;
+typedef struct ndq_plan_segment {
+  int mode;         /* NDQ_SEG_* */
+  int first, count; /* its leaves */
+  int offset, size; /* its output points */
+} ndq_plan_segment;
+typedef struct ndq_plan_sampler_desc {
+  int d;            /* output rows, 1..6 */
+  int n_leaves;     /* 1..8 */
+  int n_segments;
+  int reserved;
+  ndq_plan_leaf leaf[NDQ_PLAN_MAX_LEAVES];
+  ndq_plan_segment seg[NDQ_PLAN_MAX_LEAVES];
+} ndq_plan_sampler_desc;
+int ndq_sample_plan(const ndq_plan_sampler_desc* desc, unsigned long long seed, unsigned long long draw,
+                    unsigned stream_id, float* coords /* [d][ldc] */, int ldc, void* stream);
+
 /* Launcher exported by a generated single-network fused closure kernel (codegen.py: fused_source). */
 typedef int (*ndq_fused_launch_fn)(const float* coords, int ldc, int n, const float* params, float* partials,
                                    float* loss_partials, float* funcs, float* resid, int ldj, float seed, int train,

@@ -40,6 +40,32 @@ class TableSamplerDesc(ctypes.Structure):
                 ("hi", ctypes.c_float * 6)]
 
 
+NDQ_PLAN_MAX_LEAVES = 8
+NDQ_LEAF_SIMPLE, NDQ_LEAF_TABLE, NDQ_LEAF_DATA = 0, 1, 2
+NDQ_SEG_LEAF, NDQ_SEG_ENSEMBLE, NDQ_SEG_MESH = 0, 1, 2
+
+
+class _PlanLaw(ctypes.Union):
+    _fields_ = [("simple", SamplerDesc), ("table", TableSamplerDesc), ("data", ctypes.c_void_p * 6)]
+
+
+class PlanLeaf(ctypes.Structure):
+    """ndq_plan_leaf of include/ndq.h"""
+    _fields_ = [("kind", ctypes.c_int), ("row0", ctypes.c_int), ("rows", ctypes.c_int), ("n", ctypes.c_int), ("u", _PlanLaw)]
+
+
+class PlanSegment(ctypes.Structure):
+    """ndq_plan_segment of include/ndq.h"""
+    _fields_ = [("mode", ctypes.c_int), ("first", ctypes.c_int), ("count", ctypes.c_int), ("offset", ctypes.c_int),
+                ("size", ctypes.c_int)]
+
+
+class PlanSamplerDesc(ctypes.Structure):
+    """ndq_plan_sampler_desc of include/ndq.h"""
+    _fields_ = [("d", ctypes.c_int), ("n_leaves", ctypes.c_int), ("n_segments", ctypes.c_int), ("reserved", ctypes.c_int),
+                ("leaf", PlanLeaf * 8), ("seg", PlanSegment * 8)]
+
+
 FUSED_LAUNCH_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                    ctypes.c_float, ctypes.c_int, ctypes.c_void_p)
@@ -112,6 +138,7 @@ def lib():
     L.ndq_sample.argtypes = [ctypes.POINTER(SamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci, vp]
     L.ndq_sample_table.argtypes = [ctypes.POINTER(TableSamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci,
                                    vp]
+    L.ndq_sample_plan.argtypes = [ctypes.POINTER(PlanSamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci, vp]
     L.ndq_oneshot_create.argtypes = [ci, ci, ci, ctypes.POINTER(vp), ctypes.c_char_p]
     L.ndq_oneshot_connect.argtypes = [vp, ctypes.c_char_p]
     L.ndq_oneshot_allreduce.argtypes = [vp, vp, ctypes.c_size_t, ci, ci, vp, vp]
@@ -119,7 +146,7 @@ def lib():
     L.ndq_oneshot_destroy.argtypes = [vp]
     for name in ("ndq_mlp_supported", "ndq_mlp_num_streams", "ndq_mlp_num_params", "ndq_mlp_bwd_blocks",
                  "ndq_mlp_jet_fwd", "ndq_mlp_jet_bwd", "ndq_reduce_partials", "ndq_adam_step", "ndq_reduce_grad_loss",
-                 "ndq_epoch_tail", "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_mlp_register",
+                 "ndq_epoch_tail", "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_sample_plan", "ndq_mlp_register",
                  "ndq_fused_multi_step_run", "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect",
                  "ndq_oneshot_allreduce", "ndq_oneshot_status",
                  "ndq_oneshot_destroy"):
@@ -168,8 +195,8 @@ EXPORTS64 = ("ndq64_mlp_register", "ndq64_mlp_supported", "ndq64_mlp_num_streams
 
 EXPORTS = ("ndq_mlp_supported", "ndq_mlp_num_streams", "ndq_mlp_num_params", "ndq_mlp_bwd_blocks", "ndq_mlp_jet_fwd",
            "ndq_mlp_jet_bwd", "ndq_reduce_partials", "ndq_adam_step", "ndq_reduce_grad_loss", "ndq_epoch_tail",
-           "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_mlp_register", "ndq_fused_multi_step_run",
-           "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect", "ndq_oneshot_allreduce", "ndq_oneshot_status",
+           "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_sample_plan", "ndq_mlp_register",
+           "ndq_fused_multi_step_run", "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect", "ndq_oneshot_allreduce", "ndq_oneshot_status",
            "ndq_oneshot_destroy")
 
 

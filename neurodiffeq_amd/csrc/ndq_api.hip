@@ -828,6 +828,11 @@ int ndq_sample_table(const ndq_table_sampler_desc* desc, unsigned long long seed
   return ndq::launch_sample_table(desc, seed, draw, stream_id, coords, ldc, (hipStream_t)stream);
 }
 
+int ndq_sample_plan(const ndq_plan_sampler_desc* desc, unsigned long long seed, unsigned long long draw,
+                    unsigned stream_id, float* coords, int ldc, void* stream) {
+  return ndq::launch_sample_plan(desc, seed, draw, stream_id, coords, ldc, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------- one-shot all-reduce

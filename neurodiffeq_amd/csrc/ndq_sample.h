@@ -44,42 +44,71 @@ struct SampleArgs {
   int ldc, total;
 };
 
+// Box-Muller on one Philox block: (w0, w1) -> two normals, (w2, w3) -> a third; the words of NDQ_SAMPLE_GRID, in its order
+__device__ __forceinline__ void normals3(const U4& r, float& z0, float& z1, float& z2) {
+  const float r0 = sqrtf(-2.0f * __logf(u01_open(r.x))), t0 = 6.283185307179586f * u01(r.y);
+  const float r1 = sqrtf(-2.0f * __logf(u01_open(r.z))), t1 = 6.283185307179586f * u01(r.w);
+  z0 = r0 * __cosf(t0); z1 = r0 * __sinf(t0); z2 = r1 * __cosf(t1);
+}
+
+// Philox key and counter words 1..3 of one draw of one generator: key = seed, counter = (point, draw_lo, draw_hi, stream id)
+struct DrawKey { unsigned k0, k1, c1, c2, c3; };
+__device__ __forceinline__ U4 block_a(const DrawKey& k, int j) { return philox4x32_10(U4{(unsigned)j, k.c1, k.c2, k.c3}, k.k0, k.k1); }
+// a second block whose counter word 0 has the top bit set (at most 2^31 - 1 points: no point owns that word)
+__device__ __forceinline__ U4 block_b(const DrawKey& k, int j) {
+  return philox4x32_10(U4{(unsigned)j | 0x80000000u, k.c1, k.c2, k.c3}, k.k0, k.k1);
+}
+
+// ---- THE definition of every ndq_sampler_desc law: point j of the draw `k` of `s` -> v[0 .. s.d - 1].  Called by sample_kernel,
+// by the epoch tail kernel's prefetch workgroups and by sample_plan_kernel.  Every loop over the coordinates is unrolled with
+// `c < d` guards (no runtime-indexed private array, no scratch).  noisy == 0 (an exact grid): no Philox block is computed.
+__device__ __forceinline__ void simple_point(const ndq_sampler_desc& s, int noisy, const DrawKey& k, int j, float (&v)[3]) {
+  U4 r = U4{0u, 0u, 0u, 0u};
+  if (noisy) r = block_a(k, j);
+  if (s.kind == NDQ_SAMPLE_UNIFORM) {                       // generators.py:150-152 (Generator1D 'uniform')
+    const unsigned w[3] = {r.x, r.y, r.z};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      if (c < s.d) v[c] = s.lo[c] + (s.hi[c] - s.lo[c]) * u01(w[c]);
+  } else if (s.kind == NDQ_SAMPLE_GRID) {                   // generators.py:253-266: ij-meshgrid + N(0, std^2) jitter
+    float z[3] = {0.0f, 0.0f, 0.0f};
+    if (noisy) normals3(r, z[0], z[1], z[2]);
+    int rem = j;
+    int idx[3] = {0, 0, 0};
+#pragma unroll
+    for (int c = 2; c >= 0; --c)
+      if (c < s.d) { idx[c] = rem % s.n[c]; rem /= s.n[c]; }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      if (c < s.d) {
+        float x = linspace_at(s.lo[c], s.hi[c], s.n[c], idx[c]);
+        if (s.noise_std[c] != 0.0f) x = fmaf(s.noise_std[c], z[c], x);
+        v[c] = x;
+      }
+  } else {                                                  // generators.py:622-646 (GeneratorSpherical)
+    const float p = u01_open(r.x), q = u01_open(r.y), t = u01_open(r.z);
+    const float inv = 1.0f / (p + q + t);
+    float x = sqrtf(p * inv) + 1e-6f, y = sqrtf(q * inv) + 1e-6f, z = fminf(sqrtf(t * inv) + 1e-6f, 1.0f);
+    if (r.x & 1u) x = -x;                                   // the low 8 bits of each word are not used by u01
+    if (r.y & 1u) y = -y;
+    if (r.z & 1u) z = -z;
+    const float u = u01(r.w);
+    const float lo = s.lo[0], hi = s.hi[0];
+    v[0] = s.radial ? lo + (hi - lo) * u : sqrtf((hi * hi - lo * lo) * u + lo * lo);
+    v[1] = acosf(z);
+    v[2] = 3.14159265358979f - atan2f(y, x);
+  }
+}
+
 // point i of the batch described by a (one thread per point; also called from the epoch tail kernel's extra
 // workgroups, which draw the NEXT batch while the optimiser step is applied: csrc/ndq_api.hip)
 __device__ __forceinline__ void sample_point_store(const SampleArgs& a, int i) {
   if (i >= a.total) return;
-  const U4 r = philox4x32_10(U4{(unsigned)i, a.c1, a.c2, a.c3}, a.k0, a.k1);
-  const unsigned w[4] = {r.x, r.y, r.z, r.w};
-  const ndq_sampler_desc& s = a.s;
-  if (s.kind == NDQ_SAMPLE_UNIFORM) {                       // generators.py:150-152 (Generator1D 'uniform')
-    for (int c = 0; c < s.d; ++c) a.coords[(size_t)c * a.ldc + i] = s.lo[c] + (s.hi[c] - s.lo[c]) * u01(w[c]);
-  } else if (s.kind == NDQ_SAMPLE_GRID) {                   // generators.py:253-266: ij-meshgrid + N(0, std^2) jitter
-    // Box-Muller: (w0, w1) -> two normals, (w2, w3) -> two more
-    const float r0 = sqrtf(-2.0f * __logf(u01_open(w[0]))), t0 = 6.283185307179586f * u01(w[1]);
-    const float r1 = sqrtf(-2.0f * __logf(u01_open(w[2]))), t1 = 6.283185307179586f * u01(w[3]);
-    const float z[3] = {r0 * __cosf(t0), r0 * __sinf(t0), r1 * __cosf(t1)};
-    int rem = i;
-    int idx[3] = {0, 0, 0};
-    for (int c = s.d - 1; c >= 0; --c) { idx[c] = rem % s.n[c]; rem /= s.n[c]; }
-    for (int c = 0; c < s.d; ++c) {
-      float v = linspace_at(s.lo[c], s.hi[c], s.n[c], idx[c]);
-      if (s.noise_std[c] != 0.0f) v = fmaf(s.noise_std[c], z[c], v);
-      a.coords[(size_t)c * a.ldc + i] = v;
-    }
-  } else {                                                  // generators.py:622-646 (GeneratorSpherical)
-    const float p = u01_open(w[0]), q = u01_open(w[1]), t = u01_open(w[2]);
-    const float inv = 1.0f / (p + q + t);
-    float x = sqrtf(p * inv) + 1e-6f, y = sqrtf(q * inv) + 1e-6f, z = fminf(sqrtf(t * inv) + 1e-6f, 1.0f);
-    if (w[0] & 1u) x = -x;                                  // the low 8 bits of each word are not used by u01
-    if (w[1] & 1u) y = -y;
-    if (w[2] & 1u) z = -z;
-    const float u = u01(w[3]);
-    const float lo = s.lo[0], hi = s.hi[0];
-    const float rad = s.radial ? lo + (hi - lo) * u : sqrtf((hi * hi - lo * lo) * u + lo * lo);
-    a.coords[i] = rad;
-    a.coords[(size_t)a.ldc + i] = acosf(z);
-    a.coords[(size_t)2 * a.ldc + i] = 3.14159265358979f - atan2f(y, x);
-  }
+  float v[3] = {0.0f, 0.0f, 0.0f};
+  simple_point(a.s, 1, DrawKey{a.k0, a.k1, a.c1, a.c2, a.c3}, i, v);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    if (c < a.s.d) a.coords[(size_t)c * a.ldc + i] = v[c];
 }
 
 __global__ void __launch_bounds__(256) sample_kernel(SampleArgs a) { sample_point_store(a, blockIdx.x * 256 + threadIdx.x); }
@@ -129,37 +158,27 @@ struct TableArgs {
   int ldc, total, noisy;      // noisy == 0: no axis has a width table or a random law -- no Philox block is computed
 };
 
-// two Box-Muller pairs of one Philox block, three of the four normals: the words of NDQ_SAMPLE_GRID, in its order
-__device__ __forceinline__ void normals3(const U4& r, float& z0, float& z1, float& z2) {
-  const float r0 = sqrtf(-2.0f * __logf(u01_open(r.x))), t0 = 6.283185307179586f * u01(r.y);
-  const float r1 = sqrtf(-2.0f * __logf(u01_open(r.z))), t1 = 6.283185307179586f * u01(r.w);
-  z0 = r0 * __cosf(t0); z1 = r0 * __sinf(t0); z2 = r1 * __cosf(t1);
-}
-
-// One thread per point; every loop over the axes is unrolled to NDQ_TABLE_MAX_AXES with `c < d` guards so that n / idx /
-// z stay in registers (no runtime-indexed private array, no scratch).  Stores: consecutive lanes -> consecutive floats
-// of each SoA row.  Table reads: axis c repeats an entry over prod(n[c+1..]) consecutive points -- L1/L2 hits; in 1-D the
-// table is streamed once, coalesced.
-__global__ void __launch_bounds__(256) sample_table_kernel(TableArgs a) {
-  const unsigned iu = blockIdx.x * 256u + threadIdx.x;      // (unsigned: the last workgroup of a 2^31 - 1 point draw)
-  if (iu >= (unsigned)a.total) return;
-  const int i = (int)iu;
-  const ndq_table_sampler_desc& s = a.s;
+// ---- THE definition of every ndq_table_sampler_desc law: point j of the draw `k` of `s` -> v[0 .. s.d - 1] (sample_table_kernel,
+// sample_plan_kernel).  Every loop over the axes is unrolled to NDQ_TABLE_MAX_AXES with `c < d` guards so that n / idx / z
+// stay in registers (no runtime-indexed private array, no scratch).  noisy == 0: no axis has a width table or a random
+// law -- no Philox block is computed; block B only for d > 3.  Table reads: axis c repeats an entry over
+// prod(n[c+1..]) consecutive points -- L1/L2 hits; in 1-D the table is streamed once, coalesced.
+__device__ __forceinline__ void table_point(const ndq_table_sampler_desc& s, int noisy, const DrawKey& k, int j,
+                                            float (&v)[NDQ_TABLE_MAX_AXES]) {
   // (fill_table_args admits CHEB2_NOISY on axis 0 of a one-axis descriptor only, so law[0] decides for the whole draw)
   if (s.law[0] == NDQ_AXIS_CHEB2_NOISY) {                   // generators.py:32-34 (_chebyshev_second_noisy); d == 1
-    const U4 r = philox4x32_10(U4{(unsigned)i, a.c1, a.c2, a.c3}, a.k0, a.k1);
-    const float t = ((float)i + (2.0f * u01(r.x) - 1.0f)) / (float)(s.n[0] - 1) * 3.14159265358979f;
+    const U4 r = block_a(k, j);
+    const float t = ((float)j + (2.0f * u01(r.x) - 1.0f)) / (float)(s.n[0] - 1) * 3.14159265358979f;
     const float lo = s.lo[0], hi = s.hi[0];
-    a.coords[i] = ((lo + hi) + (hi - lo) * cosf(t)) / 2.0f;
+    v[0] = ((lo + hi) + (hi - lo) * cosf(t)) / 2.0f;
     return;
   }
   float z[NDQ_TABLE_MAX_AXES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  if (a.noisy) {
-    normals3(philox4x32_10(U4{(unsigned)i, a.c1, a.c2, a.c3}, a.k0, a.k1), z[0], z[1], z[2]);
-    // axes 3..5: a second block whose counter word 0 has the top bit set (total <= 2^31 - 1: no point owns that word)
-    if (s.d > 3) normals3(philox4x32_10(U4{(unsigned)i | 0x80000000u, a.c1, a.c2, a.c3}, a.k0, a.k1), z[3], z[4], z[5]);
+  if (noisy) {
+    normals3(block_a(k, j), z[0], z[1], z[2]);
+    if (s.d > 3) normals3(block_b(k, j), z[3], z[4], z[5]);
   }
-  unsigned rem = (unsigned)i;
+  unsigned rem = (unsigned)j;
   int idx[NDQ_TABLE_MAX_AXES] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int c = NDQ_TABLE_MAX_AXES - 1; c >= 0; --c)
@@ -167,14 +186,26 @@ __global__ void __launch_bounds__(256) sample_table_kernel(TableArgs a) {
 #pragma unroll
   for (int c = 0; c < NDQ_TABLE_MAX_AXES; ++c)
     if (c < s.d) {
-      float v = s.mean[c][idx[c]];
+      float x = s.mean[c][idx[c]];
       if (s.std[c]) {
         const float w = s.std[c][idx[c]];
-        if (w != 0.0f) v = fmaf(w, z[c], v);
+        if (w != 0.0f) x = fmaf(w, z[c], x);
       }
-      if (s.abs_value) v = fabsf(v);
-      a.coords[(size_t)c * a.ldc + i] = v;
+      if (s.abs_value) x = fabsf(x);
+      v[c] = x;
     }
+}
+
+// One thread per point.  Stores: consecutive lanes -> consecutive floats of each SoA row.
+__global__ void __launch_bounds__(256) sample_table_kernel(TableArgs a) {
+  const unsigned iu = blockIdx.x * 256u + threadIdx.x;      // (unsigned: the last workgroup of a 2^31 - 1 point draw)
+  if (iu >= (unsigned)a.total) return;
+  const int i = (int)iu;
+  float v[NDQ_TABLE_MAX_AXES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  table_point(a.s, a.noisy, DrawKey{a.k0, a.k1, a.c1, a.c2, a.c3}, i, v);
+#pragma unroll
+  for (int c = 0; c < NDQ_TABLE_MAX_AXES; ++c)
+    if (c < a.s.d) a.coords[(size_t)c * a.ldc + i] = v[c];
 }
 
 // validated launch arguments of one table draw; returns 0 or NDQ_EINVAL (nothing is launched on NDQ_EINVAL)
@@ -211,6 +242,151 @@ inline int launch_sample_table(const ndq_table_sampler_desc* s, unsigned long lo
   const int rc = fill_table_args(a, s, seed, draw, stream_id, coords, ldc);
   if (rc) return rc;
   hipLaunchKernelGGL(sample_table_kernel, dim3(((unsigned)a.total + 255u) / 256u), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------- plan sampler
+// include/ndq.h: ndq_sample_plan.  Composed generators (g1 + g2, g1 * g2, g1 ^ g2 over leaf generators) in ONE launch.
+// The host flattens the plan into one record per LEAF: which output points its segment owns, how an output point maps to
+// the leaf-local index, which rows it writes and under which key it draws.
+struct PlanLeaf {
+  int kind, row0, rows, noisy;     // noisy == 0: an exact leaf (exact nodes, DATA) -- no Philox block
+  unsigned off, size;              // its segment's output points: [off, off + size)
+  unsigned div, n;                 // MESH factor: local index = (i - off) / div % n (div = product of the later factors' sizes);
+                                   // div == 0 (LEAF / ENSEMBLE): local index = i - off
+  unsigned k0, k1;                 // seed + l * 0x9E3779B97F4A7C15
+  union {
+    ndq_sampler_desc simple;
+    ndq_table_sampler_desc table;
+    const float* data[NDQ_TABLE_MAX_AXES];
+  } u;
+};
+struct PlanArgs {                  // by value: 8 x 240 + 40 bytes of the 4 KB kernarg segment
+  PlanLeaf leaf[NDQ_PLAN_MAX_LEAVES];
+  int n_leaves;
+  unsigned c1, c2, c3;
+  float* coords;
+  int ldc, total;
+};
+static_assert(sizeof(PlanArgs) <= 2048, "PlanArgs is passed by value");
+
+// One thread per output point.  The loop runs over the LEAVES, not over the thread's own segment: the trip count and the
+// index into a.leaf are wave-uniform, so every descriptor field is a scalar load from the kernarg segment and a wave none
+// of whose lanes lies in a leaf's segment skips it in one branch; lanes diverge only in the waves that straddle a
+// segment boundary.  Each leaf's values come from the value functions above (one definition of every law); its rows are
+// stored at coords[(row0 + c) * ldc + i]: consecutive lanes -> consecutive floats of every row.
+__global__ void __launch_bounds__(256) sample_plan_kernel(PlanArgs a) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;       // (unsigned: the last workgroup of a 2^31 - 1 point draw)
+  if (i >= (unsigned)a.total) return;
+  for (int l = 0; l < a.n_leaves; ++l) {
+    const PlanLeaf& L = a.leaf[l];
+    const unsigned rel = i - L.off;
+    if (rel >= L.size) continue;
+    const int j = (int)(L.div ? rel / L.div % L.n : rel);
+    const DrawKey k{L.k0, L.k1, a.c1, a.c2, a.c3};
+    float v[NDQ_TABLE_MAX_AXES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (L.kind == NDQ_LEAF_SIMPLE) {
+      float s[3] = {0.0f, 0.0f, 0.0f};
+      simple_point(L.u.simple, L.noisy, k, j, s);
+      v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+    } else if (L.kind == NDQ_LEAF_TABLE) {
+      table_point(L.u.table, L.noisy, k, j, v);
+    } else {
+#pragma unroll
+      for (int c = 0; c < NDQ_TABLE_MAX_AXES; ++c)
+        if (c < L.rows) v[c] = L.u.data[c][j];
+    }
+#pragma unroll
+    for (int c = 0; c < NDQ_TABLE_MAX_AXES; ++c)
+      if (c < L.rows) a.coords[(size_t)(L.row0 + c) * a.ldc + i] = v[c];
+  }
+}
+
+// validated launch arguments of one plan draw; returns 0 or NDQ_EINVAL (nothing is launched on NDQ_EINVAL)
+inline int fill_plan_args(PlanArgs& a, const ndq_plan_sampler_desc* p, unsigned long long seed, unsigned long long draw,
+                          unsigned stream_id, float* coords, int ldc) {
+  if (!p || !coords || p->d < 1 || p->d > NDQ_TABLE_MAX_AXES) return NDQ_EINVAL;
+  if (p->n_leaves < 1 || p->n_leaves > NDQ_PLAN_MAX_LEAVES || p->n_segments < 1 || p->n_segments > p->n_leaves) return NDQ_EINVAL;
+  a = PlanArgs{};                                           // (unused leaf records: zeros, not stack bytes)
+  long long total = 0;
+  int next_leaf = 0;
+  for (int s = 0; s < p->n_segments; ++s) {
+    const ndq_plan_segment& g = p->seg[s];
+    if (g.mode != NDQ_SEG_LEAF && g.mode != NDQ_SEG_ENSEMBLE && g.mode != NDQ_SEG_MESH) return NDQ_EINVAL;
+    if (g.first != next_leaf || g.count < 1 || g.count > p->n_leaves - next_leaf) return NDQ_EINVAL;
+    if (g.mode == NDQ_SEG_LEAF && g.count != 1) return NDQ_EINVAL;
+    if (g.size < 1 || g.offset != total) return NDQ_EINVAL;
+    unsigned covered = 0;
+    long long product = 1;
+    for (int l = g.first; l < g.first + g.count; ++l) {
+      const ndq_plan_leaf& f = p->leaf[l];
+      PlanLeaf& o = a.leaf[l];
+      long long n = 0;
+      // (each leaf's own validation: its size is the `total` of its launch arguments; the block is not written here)
+      if (f.kind == NDQ_LEAF_SIMPLE) {
+        SampleArgs t;
+        if (fill_sample_args(t, &f.u.simple, seed, draw, stream_id, coords, 0x7fffffff) || f.rows != f.u.simple.d) return NDQ_EINVAL;
+        n = t.total;
+        o.noisy = f.u.simple.kind != NDQ_SAMPLE_GRID;
+        for (int c = 0; c < f.rows; ++c) o.noisy |= f.u.simple.noise_std[c] != 0.0f;
+        o.u.simple = f.u.simple;
+      } else if (f.kind == NDQ_LEAF_TABLE) {
+        TableArgs t;
+        if (fill_table_args(t, &f.u.table, seed, draw, stream_id, coords, 0x7fffffff) || f.rows != f.u.table.d) return NDQ_EINVAL;
+        n = t.total;
+        o.noisy = t.noisy;
+        o.u.table = f.u.table;
+      } else if (f.kind == NDQ_LEAF_DATA) {
+        if (f.rows < 1 || f.rows > NDQ_TABLE_MAX_AXES || f.n < 1) return NDQ_EINVAL;
+        for (int c = 0; c < NDQ_TABLE_MAX_AXES; ++c) {
+          if (c < f.rows && !f.u.data[c]) return NDQ_EINVAL;
+          o.u.data[c] = c < f.rows ? f.u.data[c] : nullptr;
+        }
+        n = f.n;
+        o.noisy = 0;
+      } else {
+        return NDQ_EINVAL;
+      }
+      if (f.row0 < 0 || f.row0 + f.rows > p->d) return NDQ_EINVAL;
+      const unsigned mask = ((1u << f.rows) - 1u) << f.row0;
+      if (covered & mask) return NDQ_EINVAL;
+      covered |= mask;
+      if (g.mode == NDQ_SEG_MESH) {
+        if (f.rows != 1) return NDQ_EINVAL;
+        product *= n;
+        if (product > 0x7fffffffLL) return NDQ_EINVAL;
+      } else if (n != g.size) {
+        return NDQ_EINVAL;
+      }
+      const unsigned long long key = seed + (unsigned long long)l * 0x9E3779B97F4A7C15ull;
+      o.kind = f.kind; o.row0 = f.row0; o.rows = f.rows;
+      o.off = (unsigned)g.offset; o.size = (unsigned)g.size;
+      o.div = 0u; o.n = (unsigned)n;
+      o.k0 = (unsigned)key; o.k1 = (unsigned)(key >> 32);
+    }
+    if (covered != (1u << p->d) - 1u) return NDQ_EINVAL;
+    if (g.mode == NDQ_SEG_MESH) {
+      if (product != g.size) return NDQ_EINVAL;
+      unsigned div = 1u;                                    // last factor fastest
+      for (int l = g.first + g.count - 1; l >= g.first; --l) { a.leaf[l].div = div; div *= a.leaf[l].n; }
+    }
+    next_leaf += g.count;
+    total += g.size;
+    if (total > 0x7fffffffLL) return NDQ_EINVAL;
+  }
+  if (next_leaf != p->n_leaves || ldc < total) return NDQ_EINVAL;
+  a.n_leaves = p->n_leaves;
+  a.c1 = (unsigned)draw; a.c2 = (unsigned)(draw >> 32); a.c3 = stream_id;
+  a.coords = coords; a.ldc = ldc; a.total = (int)total;
+  return 0;
+}
+
+inline int launch_sample_plan(const ndq_plan_sampler_desc* p, unsigned long long seed, unsigned long long draw,
+                              unsigned stream_id, float* coords, int ldc, hipStream_t stream) {
+  PlanArgs a;
+  const int rc = fill_plan_args(a, p, seed, draw, stream_id, coords, ldc);
+  if (rc) return rc;
+  hipLaunchKernelGGL(sample_plan_kernel, dim3(((unsigned)a.total + 255u) / 256u), dim3(256), 0, stream, a);
   return (int)hipGetLastError();
 }
 

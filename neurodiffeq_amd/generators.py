@@ -731,7 +731,8 @@ def table_spec(g):
     """:class:`TableSpec` of a generator the table sampler (``ndq_sample_table``) can draw: ``GeneratorND`` (every method,
     ``cut``, ``noisy`` or not, ``abs_value``, up to six axes) and the node-table laws of ``Generator1D``.  The tables are the
     tensors the generator built for itself, so exact nodes are the reference's own numbers.  ``ValueError`` for everything
-    else: 'latin-hypercube' (a permutation: index sampling stays on the host), the wrapper generators, and a ``GeneratorND``
+    else: 'latin-hypercube' (a permutation: index sampling stays on the host), the wrapper generators (``g1 + g2``, ``g1 * g2``,
+    ``g1 ^ g2``, Static / Predefined generators are composed from leaf laws by :func:`plan_spec`, not here), and a ``GeneratorND``
     whose ``grid_r`` / ``grid_std`` -- what its own getter draws from -- are no longer the meshgrids of its per-axis tensors
     (replaced or edited after construction: the tables would draw another law than the host getter)."""
     from . import _lib
@@ -754,6 +755,139 @@ def table_spec(g):
     if type(g) is Generator1D and g.method == "chebyshev2-noisy":
         return TableSpec([int(g.size)], [cheb2n], [None], [None], [float(g.t_min)], [float(g.t_max)], False)
     raise ValueError(f"the table sampler cannot draw {g!r} on the device")
+
+
+class PlanLeaf:
+    """One leaf of a :class:`PlanSpec`: ``kind`` 'simple' (``desc``: the ``ndq_sampler_desc`` of :meth:`DeviceGenerator.describe`),
+    'table' (``table``: the :class:`TableSpec`) or 'data' (``data``: the generator's fixed tensors as fp32 rows); ``row0`` /
+    ``rows``: the output rows it writes; ``size``: its number of points; ``live``: the attributes it reads when it draws."""
+
+    def __init__(self, gen, kind, rows, size, live, desc=None, table=None, data=None):
+        self.gen, self.kind, self.rows, self.size, self.live = gen, kind, rows, size, live
+        self.desc, self.table, self.data, self.row0 = desc, table, data, 0
+
+
+class PlanSpec:
+    """Host-side description of a composed draw (``ndq_plan_sampler_desc`` minus the device pointers): ``leaves`` numbered
+    depth-first from 0, ``segments`` = [(mode, first leaf, leaf count, point offset, points)] with mode 'leaf' / 'ensemble' /
+    'mesh', ``d`` rows, ``size`` points in all, ``wrappers``: every Concat / Ensemble / Mesh node of the tree."""
+
+    def __init__(self, d, size, leaves, segments, wrappers):
+        self.d, self.size, self.leaves, self.segments, self.wrappers = d, size, leaves, segments, wrappers
+
+
+PLAN_MAX_LEAVES = 8
+#: leaf l of a plan draws under this seed (leaf 0: ``seed`` itself); two leaves never share a Philox key
+plan_leaf_seed = lambda seed, l: (int(seed) + l * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+
+def _plan_leaf(g):
+    if isinstance(g, (ConcatGenerator, EnsembleGenerator, MeshGenerator)):
+        raise ValueError(f"{g!r} is a wrapper, not a leaf")           # (callers name the nesting)
+    if isinstance(g, (StaticGenerator, PredefinedGenerator)):          # DATA: the fixed tensors themselves, whatever is wrapped
+        name = "examples" if isinstance(g, StaticGenerator) else "xs"
+        ex = getattr(g, name)
+        ex = [ex] if isinstance(ex, torch.Tensor) else list(ex)
+        if not ex or any((not isinstance(e, torch.Tensor)) or e.dtype != torch.float32 or e.numel() != ex[0].numel() for e in ex):
+            raise ValueError(f"the fixed points of {g!r} are not float32 tensors of one length: they cannot be handed out exactly")
+        if ex[0].numel() < 1:
+            raise ValueError(f"{g!r} holds no points")
+        return PlanLeaf(g, "data", len(ex), ex[0].numel(), (name,), data=[_f32(e).reshape(-1) for e in ex])
+    if isinstance(g, Generator1D) and g.method == "latin-hypercube":
+        raise ValueError(f"'latin-hypercube' is a permutation and stays on the host, alone or inside a wrapper: {g!r}")
+    try:
+        desc = DeviceGenerator.describe(g)
+        from . import _lib
+        size = int(np.prod(list(desc.n)[:desc.d])) if desc.kind == _lib.NDQ_SAMPLE_GRID else int(desc.n[0])
+        return PlanLeaf(g, "simple", int(desc.d), size, _LIVE, desc=desc)
+    except ValueError:
+        pass
+    try:
+        spec = table_spec(g)
+    except ValueError:
+        raise ValueError(f"the device sampler cannot draw {g!r} (neither a leaf law nor Concat / Ensemble / Mesh)") from None
+    return PlanLeaf(g, "table", spec.d, int(np.prod(spec.n)), _LIVE_TABLE, table=spec)
+
+
+def plan_spec(g):
+    """:class:`PlanSpec` of a composed generator the plan sampler (``ndq_sample_plan``) draws in one launch.  Normal form::
+
+        plan    := Concat[segment, ...]                       (a lone segment is a plan of one segment)
+        segment := leaf | Ensemble[leaf, ...] | Mesh[one-row leaf, ...]
+        leaf    := what DeviceGenerator.describe accepts | what table_spec accepts
+                 | PredefinedGenerator | StaticGenerator     (DATA: its fixed float32 tensors, uploaded once, exact)
+
+    Concat inside Concat and Ensemble inside Ensemble are flattened (MeshGenerator flattens itself).  Leaves are numbered
+    depth-first from 0; leaf ``l`` draws under ``plan_leaf_seed(seed, l)`` with its leaf-local point index as Philox counter
+    word 0, so a composed draw is the ``torch.cat`` / tuple / ``torch.meshgrid(indexing="ij")`` composition of what
+    ``DeviceGenerator(leaf, seed=plan_leaf_seed(seed, l))`` hands out -- two leaves never share a key, the same object used
+    twice included (the reference draws ``g ^ g`` as two independent draws), and a mesh factor's jitter at a node is the same
+    for every partner node (the reference draws each factor once, then meshgrids).  ``ValueError`` naming the node for:
+    Concat inside Mesh / Ensemble, Mesh inside Ensemble, Ensemble inside Mesh, a mesh factor of more than one row (the
+    reference makes every row an axis and gets ``size`` wrong), ensemble members of different sizes, segments with
+    different row counts, more than six rows, more than eight leaves, 'latin-hypercube', and every other wrapper
+    (Transform / Filter / Resample / Batch / Sampler generators)."""
+    wrappers, leaves, segments = [], [], []
+
+    def parts(node):                                   # Concat inside Concat: flattened
+        if isinstance(node, ConcatGenerator):
+            wrappers.append(node)
+            if not node.generators:
+                raise ValueError(f"{node!r} concatenates nothing")
+            for sub in node.generators:
+                yield from parts(sub)
+        else:
+            yield node
+
+    def members(node, kind, inside):                   # Ensemble inside Ensemble (Mesh inside Mesh): flattened
+        wrappers.append(node)
+        if not node.generators:
+            raise ValueError(f"{node!r} combines nothing")
+        for sub in node.generators:
+            if isinstance(sub, kind):
+                yield from members(sub, kind, inside)
+            elif isinstance(sub, (ConcatGenerator, EnsembleGenerator, MeshGenerator)):
+                raise ValueError(f"{type(sub).__name__} inside {inside} is outside the plan sampler's normal form: {sub!r} in {node!r}")
+            else:
+                yield sub
+
+    d = None
+    offset = 0
+    for node in parts(g):
+        first = len(leaves)
+        if isinstance(node, EnsembleGenerator):
+            mode, own = "ensemble", [_plan_leaf(m) for m in members(node, EnsembleGenerator, "EnsembleGenerator")]
+            if any(f.size != own[0].size for f in own):
+                raise ValueError(f"the members of {node!r} draw different numbers of points: {[f.size for f in own]}")
+            size, row = own[0].size, 0
+            for f in own:
+                f.row0, row = row, row + f.rows
+        elif isinstance(node, MeshGenerator):
+            mode, own = "mesh", [_plan_leaf(m) for m in members(node, MeshGenerator, "MeshGenerator")]
+            for f in own:
+                if f.rows != 1:
+                    raise ValueError(f"a mesh factor must be a one-row generator (the reference makes every row of {f.gen!r} an axis "
+                                     f"of the mesh and gets `size` wrong): {node!r}")
+            size, row = int(np.prod([f.size for f in own], dtype=np.int64)), len(own)
+            for c, f in enumerate(own):
+                f.row0 = c
+        else:
+            mode, own = "leaf", [_plan_leaf(node)]
+            size, row = own[0].size, own[0].rows
+        if d is not None and row != d:
+            raise ValueError(f"the segments of {g!r} have different numbers of rows: {node!r} has {row}, the ones before it {d}")
+        d = row
+        leaves += own
+        segments.append((mode, first, len(own), offset, size))
+        offset += size
+    from . import _lib
+    if d > _lib.NDQ_TABLE_MAX_AXES:
+        raise ValueError(f"{g!r} has {d} rows: the plan sampler writes at most {_lib.NDQ_TABLE_MAX_AXES}")
+    if len(leaves) > PLAN_MAX_LEAVES:
+        raise ValueError(f"{g!r} has {len(leaves)} leaves: the plan sampler takes at most {PLAN_MAX_LEAVES}")
+    if offset > 2 ** 31 - 1:
+        raise ValueError(f"{g!r} draws {offset} points: more than 2^31 - 1")
+    return PlanSpec(d, offset, leaves, segments, wrappers)
 
 
 # (N, 1) view lists handed out by DeviceGenerators -> the generator (engine.fast_train_epoch asks for a prefetch)
@@ -781,8 +915,13 @@ class DeviceGenerator(BaseGenerator):
     ('equally-spaced', 'equally-spaced-noisy'), ``GeneratorSpherical`` (both radial laws) through ``ndq_sample``; and, from
     per-axis node / width tables uploaded once (:func:`table_spec`, ``ndq_sample_table``): ``GeneratorND`` (1..6 axes, every
     method, ``cut``, ``noisy`` or not, ``abs_value``) and ``Generator1D`` 'log-spaced', 'log-spaced-noisy', 'chebyshev' /
-    'chebyshev1', 'chebyshev2', 'chebyshev2-noisy' (no ``prefetch`` for these).  Not drawn on the device: 'latin-hypercube' (a
-    permutation) and the wrapper generators.  ``get_examples`` enqueues
+    'chebyshev1', 'chebyshev2', 'chebyshev2-noisy' (no ``prefetch`` for these); and, composed by ONE kernel (:func:`plan_spec`,
+    ``ndq_sample_plan``, no ``prefetch`` either): ``g1 + g2`` (ConcatGenerator), ``g1 * g2`` (EnsembleGenerator) and ``g1 ^ g2``
+    (MeshGenerator) over any of the above, ``StaticGenerator`` and ``PredefinedGenerator`` (their fixed points, uploaded once and
+    handed out bit for bit); leaf ``l`` of a composition draws under ``plan_leaf_seed(seed, l)``, so the batch is the
+    composition of what a DeviceGenerator of each leaf hands out under that seed.  Not drawn on the device: 'latin-hypercube' (a
+    permutation), alone or inside a wrapper, the Transform / Filter / Resample / Batch / Sampler generators, and compositions
+    outside the normal form of :func:`plan_spec`.  ``get_examples`` enqueues
     one kernel on the current stream and returns ``(N, 1)`` views of ONE resident SoA block which the fused engine
     reads in place; the block is overwritten by the next draw (stream-ordered, so the previous step has consumed it).
     (Drawing the next batch on a side stream while the current one trains was tried: the event waits between the two
@@ -805,17 +944,26 @@ class DeviceGenerator(BaseGenerator):
         self.stream_id = int(os.environ.get("RANK", "0")) if stream_id is None else int(stream_id)
         self.draw = 0
         self.table = None            # the TableSpec when the batch is drawn by ndq_sample_table (second route), else None
+        self.plan = None             # the PlanSpec when the batch is drawn by ndq_sample_plan (third route), else None
         try:
             self.desc = self.describe(generator)
             names = _LIVE
         except ValueError:
-            spec = table_spec(generator)         # (ValueError: neither sampler draws this generator)
+            try:
+                spec, plan = table_spec(generator), None
+            except ValueError:
+                spec, plan = None, plan_spec(generator)      # (ValueError: no sampler draws this generator)
             if prefetch:
                 raise ValueError(f"prefetch=True is not available for {generator!r}: the epoch tail's prefetch draws "
                                  "ndq_sampler_desc laws only, and this generator is drawn from tables")
-            self._set_table(spec)
-            self.size = int(np.prod(spec.n))     # (GeneratorND: `cut` shortens the draw, `size` stays the product of `grid`)
-            names = _LIVE_TABLE
+            if plan is None:
+                self._set_table(spec)
+                self.size = int(np.prod(spec.n))     # (GeneratorND: `cut` shortens the draw, `size` stays the product of `grid`)
+                names = _LIVE_TABLE
+            else:
+                self._set_plan(plan)
+                self.size = plan.size                # (the points actually produced: a GeneratorND leaf counts its table size)
+                names = ()                           # (the whole tree is watched: _restamp)
         # the descriptor froze what the wrapped generator draws from; the reference reads it at every draw (generators.py:107-416),
         # so a callback that changes a noise width / replaces a grid tensor or the getter has to be seen: live_stamp per draw
         self._live_names = tuple(n for n in names if n in vars(generator))
@@ -870,25 +1018,69 @@ class DeviceGenerator(BaseGenerator):
             raise ValueError(f"DeviceGenerator cannot draw {g!r} on the device")
         return d
 
-    def _set_table(self, spec):
-        """Descriptor of the table route: every node / width table of ``spec`` in ONE device buffer (one upload, kept alive by
-        this generator), the descriptor's pointers into it."""
-        from . import _lib
-        d = _lib.TableSamplerDesc()
-        d.d, d.abs_value = spec.d, int(spec.abs_value)
+    def _upload(self, tables):
+        """{key: fp32 array} -> (ONE device buffer holding them all -- one upload, kept alive by this generator --, {key: device
+        address})."""
         parts, at, where = [], 0, {}
-        for kind, tables in (("mean", spec.mean), ("std", spec.std)):
-            for c, t in enumerate(tables):
-                if t is not None:
-                    where[kind, c] = at
-                    parts.append(np.pad(t, (0, -len(t) % 4)))      # every table starts 16-byte aligned
-                    at += len(parts[-1])
+        for key, t in tables.items():
+            where[key] = at
+            parts.append(np.pad(t, (0, -len(t) % 4)))      # every table starts 16-byte aligned
+            at += len(parts[-1])
         buf = torch.from_numpy(np.concatenate(parts) if parts else np.zeros(4, np.float32)).to(self.device)
+        return buf, {key: buf.data_ptr() + 4 * at for key, at in where.items()}
+
+    @staticmethod
+    def _spec_tables(spec, tag=()):
+        """The node / width tables of a TableSpec, keyed for _upload / _fill_table."""
+        return {tag + (kind, c): t for kind, tables in (("mean", spec.mean), ("std", spec.std)) for c, t in enumerate(tables)
+                if t is not None}
+
+    @staticmethod
+    def _fill_table(d, spec, where, tag=()):
+        d.d, d.abs_value = spec.d, int(spec.abs_value)
         for c in range(spec.d):
             d.n[c], d.law[c], d.lo[c], d.hi[c] = spec.n[c], spec.law[c], spec.lo[c], spec.hi[c]
-            d.mean[c] = buf.data_ptr() + 4 * where["mean", c] if ("mean", c) in where else None
-            d.std[c] = buf.data_ptr() + 4 * where["std", c] if ("std", c) in where else None
+            d.mean[c] = where.get(tag + ("mean", c))
+            d.std[c] = where.get(tag + ("std", c))
+
+    def _set_table(self, spec):
+        """Descriptor of the table route: every node / width table of ``spec`` in ONE device buffer, the descriptor's pointers
+        into it."""
+        from . import _lib
+        d = _lib.TableSamplerDesc()
+        buf, where = self._upload(self._spec_tables(spec))
+        self._fill_table(d, spec, where)
         self.table, self._table_buf, self.desc = spec, buf, d
+
+    def _set_plan(self, plan):
+        """Descriptor of the plan route: the node, width and DATA tables of ALL leaves in ONE device buffer, uploaded here and never
+        again; the descriptor itself travels by value with every launch (no per-draw copy to the device)."""
+        from . import _lib
+        tables = {}
+        for l, f in enumerate(plan.leaves):
+            if f.kind == "table":
+                tables.update(self._spec_tables(f.table, (l,)))
+            elif f.kind == "data":
+                tables.update({(l, "data", c): row for c, row in enumerate(f.data)})
+        buf, where = self._upload(tables)
+        d = _lib.PlanSamplerDesc()
+        d.d, d.n_leaves, d.n_segments = plan.d, len(plan.leaves), len(plan.segments)
+        for l, f in enumerate(plan.leaves):
+            leaf = d.leaf[l]
+            leaf.kind = {"simple": _lib.NDQ_LEAF_SIMPLE, "table": _lib.NDQ_LEAF_TABLE, "data": _lib.NDQ_LEAF_DATA}[f.kind]
+            leaf.row0, leaf.rows, leaf.n = f.row0, f.rows, f.size
+            if f.kind == "simple":
+                leaf.u.simple = f.desc
+            elif f.kind == "table":
+                self._fill_table(leaf.u.table, f.table, where, (l,))
+            else:
+                for c in range(f.rows):
+                    leaf.u.data[c] = where[l, "data", c]
+        modes = {"leaf": _lib.NDQ_SEG_LEAF, "ensemble": _lib.NDQ_SEG_ENSEMBLE, "mesh": _lib.NDQ_SEG_MESH}
+        for k, (mode, first, count, offset, size) in enumerate(plan.segments):
+            g = d.seg[k]
+            g.mode, g.first, g.count, g.offset, g.size = modes[mode], first, count, offset, size
+        self.plan, self._table_buf, self.desc = plan, buf, d
 
     def get_examples(self):
         if torch._C._len_torch_function_stack():          # a global default-device mode: see engine.library_code
@@ -912,12 +1104,26 @@ class DeviceGenerator(BaseGenerator):
         tensors += [e for _, elements in self._quick_l for e in elements]
         self._quick_t = tuple((v, v._version) for v in tensors if isinstance(v, torch.Tensor))
         self._quick_f = type(g).get_examples
+        # plan route: the `generators` tuple of every wrapper in the tree and every leaf under the name tuple of its kind
+        # (DATA leaves: `examples` / `xs`), by identity; their lists and tensors join the element / version checks above
+        self._quick_tree = ()
+        if self.plan is not None:
+            watched = [(w, ("generators",)) for w in self.plan.wrappers] + [(f.gen, f.live) for f in self.plan.leaves]
+            tree = tuple((vars(o), n, vars(o).get(n), type(o), type(o).get_examples) for o, names in watched for n in names if n in vars(o))
+            values = [e[2] for e in tree]
+            lists = tuple((v, tuple(v)) for v in values if isinstance(v, (list, tuple)))
+            values += [e for _, elements in lists for e in elements]
+            self._quick_tree, self._quick_l = tree, self._quick_l + lists
+            self._quick_t += tuple((v, v._version) for v in values if isinstance(v, torch.Tensor))
 
     def _unchanged(self, quick=None):
         g = self.generator
         d = g.__dict__
         for n, v in (self._quick if quick is None else quick):
             if d.get(n) is not v:
+                return False
+        for od, n, v, cls, fn in self._quick_tree:
+            if od.get(n) is not v or cls.get_examples is not fn:
                 return False
         for v, elements in self._quick_l:
             if len(v) != len(elements) or any(x is not y for x, y in zip(v, elements)):
@@ -932,6 +1138,9 @@ class DeviceGenerator(BaseGenerator):
         tensors replaced / edited in place, another getter, another size): the wrapped generator's own host draw from now on,
         copied into the resident block -- what the reference would train on."""
         g = self.generator
+        if self.plan is not None:                # (no partial rebuilds on this route: any change anywhere in the tree)
+            self._to_host()
+            return self._restamp()
         if self.table is not None:
             return self._table_changed()
         try:
@@ -998,6 +1207,8 @@ class DeviceGenerator(BaseGenerator):
         else:
             stream = ctypes.c_void_p(_raw_stream(self.device.index))       # (torch.cuda.current_stream(): ~10 us per call)
             sample = self._L.ndq_sample if self.table is None else self._L.ndq_sample_table
+            if self.plan is not None:
+                sample = self._L.ndq_sample_plan
             rc = sample(ctypes.byref(self.desc), self.seed, self.draw, self.stream_id, block.data_ptr(), block.shape[1], stream)
             if rc != 0:
                 from . import _lib
