@@ -230,6 +230,35 @@ typedef struct ndq_plan_sampler_desc {
 int ndq_sample_plan(const ndq_plan_sampler_desc* desc, unsigned long long seed, unsigned long long draw,
                     unsigned stream_id, float* coords /* [d][ldc] */, int ldc, void* stream);
 
+/* Indexed plan draw: the reference's ResampleGenerator and BatchGenerator directly above a plan, still ONE kernel with one
+ * thread per OUTPUT point, no temporary, no gather pass:  root := Batch[resampled] | resampled,  resampled := Resample[plan] | plan.
+ * Let n be the points of the plan, m the points of one (resampled) inner draw, t = `draw`.
+ *   window:    batch == 0: m output points, point i is (k, r) = (t, i).  batch > 0: `batch` output points, point i is element
+ *              g = t * batch + i of the concatenated stream of inner draws: k = g / m, r = g % m (a batch may straddle inner
+ *              draws; t * batch < 2^64).
+ *   index map: r -> plan point j at which every leaf is evaluated, under the index key S = seed + 8 * 0x9E3779B97F4A7C15
+ *              (mod 2^64; the leaves own multipliers 0..7).
+ *                NONE:    j = r  (m == n).
+ *                REPLACE: j = umulhi(w, n), w = word 0 of Philox4x32-10(counter (r, k_lo, k_hi, stream_id), key S).
+ *                PERMUTE: the swap-or-not shuffle, R = 2 * bitlen(n - 1) + 8 rounds.  Round q draws B = Philox4x32-10(counter
+ *                         (q | 0x80000000, k_lo, k_hi, stream_id), key S), K = umulhi(B.x, n); from x = r: p = (K - x) mod n,
+ *                         y = max(x, p), x <- p when the top bit of fmix32(y ^ B.y) (murmur3 finaliser) is set; j = x after R
+ *                         rounds.  A bijection of [0, n) for every n; m <= n outputs are the head of a random permutation.
+ * Every leaf draws with k in place of `draw` (counter words 1 and 2) and stores its value at plan point j in output column i.
+ * NDQ_EINVAL (nothing launched): whatever ndq_sample_plan refuses, a null index descriptor, an unknown mode, m < 1, m > n under
+ * PERMUTE, m != n under NONE, batch < 0, ldc < output points. */
+#define NDQ_INDEX_NONE 0
+#define NDQ_INDEX_PERMUTE 1
+#define NDQ_INDEX_REPLACE 2
+typedef struct ndq_plan_index_desc {
+  int mode;  /* NDQ_INDEX_* */
+  int m;     /* points of one inner draw */
+  int batch; /* 0: one inner draw per call; > 0: output points per call */
+  int reserved;
+} ndq_plan_index_desc;
+int ndq_sample_plan_indexed(const ndq_plan_sampler_desc* desc, const ndq_plan_index_desc* index, unsigned long long seed,
+                            unsigned long long draw, unsigned stream_id, float* coords /* [d][ldc] */, int ldc, void* stream);
+
 /* Launcher exported by a generated single-network fused closure kernel (codegen.py: fused_source). */
 typedef int (*ndq_fused_launch_fn)(const float* coords, int ldc, int n, const float* params, float* partials,
                                    float* loss_partials, float* funcs, float* resid, int ldj, float seed, int train,

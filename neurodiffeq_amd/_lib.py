@@ -43,6 +43,7 @@ class TableSamplerDesc(ctypes.Structure):
 NDQ_PLAN_MAX_LEAVES = 8
 NDQ_LEAF_SIMPLE, NDQ_LEAF_TABLE, NDQ_LEAF_DATA = 0, 1, 2
 NDQ_SEG_LEAF, NDQ_SEG_ENSEMBLE, NDQ_SEG_MESH = 0, 1, 2
+NDQ_INDEX_NONE, NDQ_INDEX_PERMUTE, NDQ_INDEX_REPLACE = 0, 1, 2
 
 
 class _PlanLaw(ctypes.Union):
@@ -64,6 +65,11 @@ class PlanSamplerDesc(ctypes.Structure):
     """ndq_plan_sampler_desc of include/ndq.h"""
     _fields_ = [("d", ctypes.c_int), ("n_leaves", ctypes.c_int), ("n_segments", ctypes.c_int), ("reserved", ctypes.c_int),
                 ("leaf", PlanLeaf * 8), ("seg", PlanSegment * 8)]
+
+
+class PlanIndexDesc(ctypes.Structure):
+    """ndq_plan_index_desc of include/ndq.h"""
+    _fields_ = [("mode", ctypes.c_int), ("m", ctypes.c_int), ("batch", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
 FUSED_LAUNCH_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -139,6 +145,8 @@ def lib():
     L.ndq_sample_table.argtypes = [ctypes.POINTER(TableSamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci,
                                    vp]
     L.ndq_sample_plan.argtypes = [ctypes.POINTER(PlanSamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci, vp]
+    L.ndq_sample_plan_indexed.argtypes = [ctypes.POINTER(PlanSamplerDesc), ctypes.POINTER(PlanIndexDesc), ctypes.c_ulonglong,
+                                          ctypes.c_ulonglong, ctypes.c_uint, vp, ci, vp]
     L.ndq_oneshot_create.argtypes = [ci, ci, ci, ctypes.POINTER(vp), ctypes.c_char_p]
     L.ndq_oneshot_connect.argtypes = [vp, ctypes.c_char_p]
     L.ndq_oneshot_allreduce.argtypes = [vp, vp, ctypes.c_size_t, ci, ci, vp, vp]
@@ -146,7 +154,7 @@ def lib():
     L.ndq_oneshot_destroy.argtypes = [vp]
     for name in ("ndq_mlp_supported", "ndq_mlp_num_streams", "ndq_mlp_num_params", "ndq_mlp_bwd_blocks",
                  "ndq_mlp_jet_fwd", "ndq_mlp_jet_bwd", "ndq_reduce_partials", "ndq_adam_step", "ndq_reduce_grad_loss",
-                 "ndq_epoch_tail", "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_sample_plan", "ndq_mlp_register",
+                 "ndq_epoch_tail", "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_sample_plan", "ndq_sample_plan_indexed", "ndq_mlp_register",
                  "ndq_fused_multi_step_run", "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect",
                  "ndq_oneshot_allreduce", "ndq_oneshot_status",
                  "ndq_oneshot_destroy"):
@@ -195,7 +203,7 @@ EXPORTS64 = ("ndq64_mlp_register", "ndq64_mlp_supported", "ndq64_mlp_num_streams
 
 EXPORTS = ("ndq_mlp_supported", "ndq_mlp_num_streams", "ndq_mlp_num_params", "ndq_mlp_bwd_blocks", "ndq_mlp_jet_fwd",
            "ndq_mlp_jet_bwd", "ndq_reduce_partials", "ndq_adam_step", "ndq_reduce_grad_loss", "ndq_epoch_tail",
-           "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_sample_plan", "ndq_mlp_register",
+           "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_sample_plan", "ndq_sample_plan_indexed", "ndq_mlp_register",
            "ndq_fused_multi_step_run", "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect", "ndq_oneshot_allreduce", "ndq_oneshot_status",
            "ndq_oneshot_destroy")
 

@@ -833,6 +833,11 @@ int ndq_sample_plan(const ndq_plan_sampler_desc* desc, unsigned long long seed, 
   return ndq::launch_sample_plan(desc, seed, draw, stream_id, coords, ldc, (hipStream_t)stream);
 }
 
+int ndq_sample_plan_indexed(const ndq_plan_sampler_desc* desc, const ndq_plan_index_desc* index, unsigned long long seed,
+                            unsigned long long draw, unsigned stream_id, float* coords, int ldc, void* stream) {
+  return ndq::launch_sample_plan_indexed(desc, index, seed, draw, stream_id, coords, ldc, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------- one-shot all-reduce

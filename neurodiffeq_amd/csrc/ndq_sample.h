@@ -275,15 +275,31 @@ static_assert(sizeof(PlanArgs) <= 2048, "PlanArgs is passed by value");
 // of whose lanes lies in a leaf's segment skips it in one branch; lanes diverge only in the waves that straddle a
 // segment boundary.  Each leaf's values come from the value functions above (one definition of every law); its rows are
 // stored at coords[(row0 + c) * ldc + i]: consecutive lanes -> consecutive floats of every row.
-__global__ void __launch_bounds__(256) sample_plan_kernel(PlanArgs a) {
+// The kernel is a template on the index mode (NDQ_INDEX_*; NDQ_INDEX_PLAIN: ndq_sample_plan, whose instantiation is the kernel
+// as it was before there was an index) and on its launch arguments; the indexed modes are described further down, at
+// PlanIndexArgs.
+#define NDQ_INDEX_PLAIN (-1)
+struct PlanIndexArgs;
+template <int MODE> struct PlanIndexPoint;                  // window + index map of one output point (indexed modes)
+__device__ __forceinline__ const PlanArgs& plan_args(const PlanArgs& a) { return a; }
+__device__ __forceinline__ const PlanArgs& plan_args(const PlanIndexArgs& a);
+
+template <int MODE, class Args>
+__global__ void __launch_bounds__(256) sample_plan_kernel(Args args) {
+  const PlanArgs& a = plan_args(args);
   const unsigned i = blockIdx.x * 256u + threadIdx.x;       // (unsigned: the last workgroup of a 2^31 - 1 point draw)
-  if (i >= (unsigned)a.total) return;
+  unsigned pt = 0u, k1 = 0u, k2 = 0u;                       // indexed: plan point and draw counter words of output point i
+  if constexpr (MODE == NDQ_INDEX_PLAIN) {
+    if (i >= (unsigned)a.total) return;
+  } else {
+    if (!PlanIndexPoint<MODE>::map(args, i, pt, k1, k2)) return;
+  }
   for (int l = 0; l < a.n_leaves; ++l) {
     const PlanLeaf& L = a.leaf[l];
-    const unsigned rel = i - L.off;
+    const unsigned rel = (MODE == NDQ_INDEX_PLAIN ? i : pt) - L.off;
     if (rel >= L.size) continue;
     const int j = (int)(L.div ? rel / L.div % L.n : rel);
-    const DrawKey k{L.k0, L.k1, a.c1, a.c2, a.c3};
+    const DrawKey k{L.k0, L.k1, MODE == NDQ_INDEX_PLAIN ? a.c1 : k1, MODE == NDQ_INDEX_PLAIN ? a.c2 : k2, a.c3};
     float v[NDQ_TABLE_MAX_AXES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (L.kind == NDQ_LEAF_SIMPLE) {
       float s[3] = {0.0f, 0.0f, 0.0f};
@@ -386,7 +402,121 @@ inline int launch_sample_plan(const ndq_plan_sampler_desc* p, unsigned long long
   PlanArgs a;
   const int rc = fill_plan_args(a, p, seed, draw, stream_id, coords, ldc);
   if (rc) return rc;
-  hipLaunchKernelGGL(sample_plan_kernel, dim3(((unsigned)a.total + 255u) / 256u), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL((sample_plan_kernel<NDQ_INDEX_PLAIN, PlanArgs>), dim3(((unsigned)a.total + 255u) / 256u), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------------------------- indexed plan sampler
+// include/ndq.h: ndq_sample_plan_indexed.  ResampleGenerator / BatchGenerator directly above a plan: output point i is element
+// r of inner draw k (the window), r is mapped to the plan point j (the index map), and the plan's own per-point body runs
+// at j with k as the draw number.  Philox is counter-based, so nothing is drawn twice and nothing is gathered.
+struct PlanIndexArgs {             // by value: PlanArgs + 48 bytes
+  PlanArgs p;                      // p.total = n, the points of the plan; p.c1 / p.c2 are not used (k replaces the draw number)
+  unsigned long long k0;           // inner draw of output point 0
+  unsigned r0, m, n, rounds;       // its element there; points of one inner draw; plan points; PERMUTE: 2 bitlen(n - 1) + 8
+  unsigned s0, s1;                 // the index key: seed + 8 * 0x9E3779B97F4A7C15
+  int out;                         // output points
+};
+static_assert(sizeof(PlanIndexArgs) <= 2112, "PlanIndexArgs is passed by value");
+#define NDQ_INDEX_MAX_ROUNDS 70    // n <= 2^31 - 1: 2 * 31 + 8
+
+__host__ __device__ inline unsigned fmix32(unsigned h) {   // the murmur3 finaliser
+  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h;
+}
+
+// (K_q, S_q) of round q of the swap-or-not shuffle of inner draw k: a function of (k, q) only
+__device__ __forceinline__ uint2 index_round_key(const PlanIndexArgs& a, unsigned q, unsigned c1, unsigned c2) {
+  const U4 b = philox4x32_10(U4{q | 0x80000000u, c1, c2, a.p.c3}, a.s0, a.s1);
+  return make_uint2(__umulhi(b.x, a.n), b.y);
+}
+
+// one round: x and p = (K - x) mod n are partners (the round is an involution), the pair's coin decides for both
+__device__ __forceinline__ unsigned swap_or_not(unsigned x, uint2 ks, unsigned n) {
+  const unsigned p = ks.x >= x ? ks.x - x : ks.x + n - x;
+  return (fmix32(max(x, p) ^ ks.y) & 0x80000000u) ? p : x;
+}
+
+__device__ __forceinline__ const PlanArgs& plan_args(const PlanIndexArgs& a) { return a.p; }
+
+// Output point i of sample_plan_kernel<MODE, PlanIndexArgs>: window -> index map -> (plan point pt, counter words c1 / c2 of
+// its inner draw); false: i is past the last output point.  PERMUTE: the trip count `rounds` is wave-uniform and fixed by n (no
+// data-dependent loop).  The round keys depend on (k, q) only, so a workgroup all of whose points lie in ONE inner draw lets
+// thread q compute round q once into LDS (rounds x 8 bytes; every lane then reads the same address: a broadcast); a workgroup
+// that straddles an inner-draw boundary computes them per thread (same numbers).  Which of the two is decided from blockIdx
+// and launch arguments alone: workgroup-uniform, so the barrier is reached by all threads or by none, before any returns.
+template <int MODE>
+struct PlanIndexPoint {
+  static __device__ __forceinline__ bool map(const PlanIndexArgs& a, unsigned i, unsigned& pt, unsigned& c1, unsigned& c2) {
+    const unsigned u = a.r0 + i;                            // (r0 < m <= 2^31 - 1, i < 2^31 + 255: no wrap)
+    const unsigned ki = u / a.m, r = u - ki * a.m;
+    const unsigned long long k = a.k0 + ki;
+    c1 = (unsigned)k; c2 = (unsigned)(k >> 32);
+    pt = r;
+    if constexpr (MODE == NDQ_INDEX_REPLACE) {
+      pt = __umulhi(philox4x32_10(U4{r, c1, c2, a.p.c3}, a.s0, a.s1).x, a.n);
+    } else if constexpr (MODE == NDQ_INDEX_PERMUTE) {
+      __shared__ uint2 keys[NDQ_INDEX_MAX_ROUNDS + 2];
+      const unsigned u_first = a.r0 + blockIdx.x * 256u;
+      const unsigned u_last = min(u_first + 255u, a.r0 + (unsigned)a.out - 1u);
+      const bool one_draw = u_first / a.m == u_last / a.m;
+      if (one_draw) {
+        const unsigned long long kw = a.k0 + u_first / a.m;
+        if (threadIdx.x < a.rounds) keys[threadIdx.x] = index_round_key(a, threadIdx.x, (unsigned)kw, (unsigned)(kw >> 32));
+        __syncthreads();
+      }
+      if (i >= (unsigned)a.out) return false;
+      unsigned x = r;
+      if (one_draw) {
+        for (unsigned q = 0; q < a.rounds; ++q) x = swap_or_not(x, keys[q], a.n);
+      } else {
+        for (unsigned q = 0; q < a.rounds; ++q) x = swap_or_not(x, index_round_key(a, q, c1, c2), a.n);
+      }
+      pt = x;
+    }
+    return i < (unsigned)a.out;
+  }
+};
+
+// validated launch arguments of one indexed plan draw; returns 0 or NDQ_EINVAL (nothing is launched on NDQ_EINVAL)
+inline int fill_plan_index_args(PlanIndexArgs& a, const ndq_plan_sampler_desc* p, const ndq_plan_index_desc* ix, unsigned long long seed,
+                                unsigned long long draw, unsigned stream_id, float* coords, int ldc) {
+  // (the plan itself: as for ndq_sample_plan; its `ldc >= n` does not apply -- the block holds the OUTPUT points)
+  const int rc = fill_plan_args(a.p, p, seed, draw, stream_id, coords, 0x7fffffff);
+  if (rc) return rc;
+  if (!ix) return NDQ_EINVAL;
+  const int n = a.p.total;
+  if (ix->mode != NDQ_INDEX_NONE && ix->mode != NDQ_INDEX_PERMUTE && ix->mode != NDQ_INDEX_REPLACE) return NDQ_EINVAL;
+  if (ix->m < 1 || ix->batch < 0) return NDQ_EINVAL;
+  if (ix->mode == NDQ_INDEX_PERMUTE && ix->m > n) return NDQ_EINVAL;
+  if (ix->mode == NDQ_INDEX_NONE && ix->m != n) return NDQ_EINVAL;
+  const int out = ix->batch ? ix->batch : ix->m;
+  if (ldc < out) return NDQ_EINVAL;
+  a.p.ldc = ldc;
+  a.m = (unsigned)ix->m; a.n = (unsigned)n; a.out = out;
+  if (ix->batch) {
+    const unsigned long long g0 = draw * (unsigned long long)ix->batch;
+    a.k0 = g0 / a.m; a.r0 = (unsigned)(g0 % a.m);
+  } else {
+    a.k0 = draw; a.r0 = 0u;
+  }
+  unsigned bits = 0u;
+  for (unsigned v = a.n - 1u; v; v >>= 1) ++bits;
+  a.rounds = 2u * bits + 8u;
+  const unsigned long long key = seed + 8ull * 0x9E3779B97F4A7C15ull;
+  a.s0 = (unsigned)key; a.s1 = (unsigned)(key >> 32);
+  return 0;
+}
+
+inline int launch_sample_plan_indexed(const ndq_plan_sampler_desc* p, const ndq_plan_index_desc* ix, unsigned long long seed,
+                                      unsigned long long draw, unsigned stream_id, float* coords, int ldc, hipStream_t stream) {
+  PlanIndexArgs a;
+  const int rc = fill_plan_index_args(a, p, ix, seed, draw, stream_id, coords, ldc);
+  if (rc) return rc;
+  const dim3 grid(((unsigned)a.out + 255u) / 256u), block(256);
+  if (ix->mode == NDQ_INDEX_PERMUTE) hipLaunchKernelGGL((sample_plan_kernel<NDQ_INDEX_PERMUTE, PlanIndexArgs>), grid, block, 0, stream, a);
+  else if (ix->mode == NDQ_INDEX_REPLACE) hipLaunchKernelGGL((sample_plan_kernel<NDQ_INDEX_REPLACE, PlanIndexArgs>), grid, block, 0, stream, a);
+  else hipLaunchKernelGGL((sample_plan_kernel<NDQ_INDEX_NONE, PlanIndexArgs>), grid, block, 0, stream, a);
   return (int)hipGetLastError();
 }
 

@@ -67,6 +67,9 @@ _LIVE = ("getter", "get_r", "examples", "grid_x", "grid_y", "grid_z", "noise_std
 #: the same for the generators DeviceGenerator draws from tables (GeneratorND, the node-table laws of Generator1D); a tuple of its
 #: own: _LIVE also feeds the bulk-draw stamp of the other generators
 _LIVE_TABLE = ("grid_r", "grid_std", "getter", "examples", "noise_std", "size", "method")
+#: what a ResampleGenerator / BatchGenerator above a plan reads when it draws (BatchGenerator.cached_xs is host state: the device
+#: draw has no cache, its window is a function of the draw number)
+_LIVE_INDEX = ("size", "replacement", "generator")
 
 
 def live_stamp(gen, names=_LIVE):
@@ -731,8 +734,9 @@ def table_spec(g):
     """:class:`TableSpec` of a generator the table sampler (``ndq_sample_table``) can draw: ``GeneratorND`` (every method,
     ``cut``, ``noisy`` or not, ``abs_value``, up to six axes) and the node-table laws of ``Generator1D``.  The tables are the
     tensors the generator built for itself, so exact nodes are the reference's own numbers.  ``ValueError`` for everything
-    else: 'latin-hypercube' (a permutation: index sampling stays on the host), the wrapper generators (``g1 + g2``, ``g1 * g2``,
-    ``g1 ^ g2``, Static / Predefined generators are composed from leaf laws by :func:`plan_spec`, not here), and a ``GeneratorND``
+    else: 'latin-hypercube' (a permutation of jittered strata: stays on the host), the wrapper generators (``g1 + g2``, ``g1 * g2``,
+    ``g1 ^ g2``, Static / Predefined generators and a root-level Resample / Batch are composed from leaf laws by :func:`plan_spec`,
+    not here), and a ``GeneratorND``
     whose ``grid_r`` / ``grid_std`` -- what its own getter draws from -- are no longer the meshgrids of its per-axis tensors
     (replaced or edited after construction: the tables would draw another law than the host getter)."""
     from . import _lib
@@ -767,18 +771,33 @@ class PlanLeaf:
         self.desc, self.table, self.data, self.row0 = desc, table, data, 0
 
 
+class PlanIndex:
+    """The root-level Resample / Batch part of a :class:`PlanSpec` (``ndq_plan_index_desc``): ``mode`` 'none' | 'permute' (a
+    ResampleGenerator without replacement) | 'replace' (with), ``n`` points of the plan, ``m`` points of one (resampled) inner draw
+    (``m == n`` without a Resample), ``batch``: 0, or the BatchGenerator's batch size."""
+
+    def __init__(self, mode, n, m, batch):
+        self.mode, self.n, self.m, self.batch = mode, n, m, batch
+
+
 class PlanSpec:
     """Host-side description of a composed draw (``ndq_plan_sampler_desc`` minus the device pointers): ``leaves`` numbered
     depth-first from 0, ``segments`` = [(mode, first leaf, leaf count, point offset, points)] with mode 'leaf' / 'ensemble' /
-    'mesh', ``d`` rows, ``size`` points in all, ``wrappers``: every Concat / Ensemble / Mesh node of the tree."""
+    'mesh', ``d`` rows, ``size`` points handed out per draw, ``wrappers``: every Concat / Ensemble / Mesh node of the tree (and the
+    root-level Resample / Batch nodes), ``index``: None, or the :class:`PlanIndex` of a Resample / Batch root -- ``size`` is then
+    ``index.batch or index.m``, the plan's own points are ``index.n``."""
 
-    def __init__(self, d, size, leaves, segments, wrappers):
-        self.d, self.size, self.leaves, self.segments, self.wrappers = d, size, leaves, segments, wrappers
+    def __init__(self, d, size, leaves, segments, wrappers, index=None):
+        self.d, self.leaves, self.segments, self.wrappers, self.index = d, leaves, segments, wrappers, index
+        self.size = size if index is None else (index.batch or index.m)
 
 
 PLAN_MAX_LEAVES = 8
 #: leaf l of a plan draws under this seed (leaf 0: ``seed`` itself); two leaves never share a Philox key
 plan_leaf_seed = lambda seed, l: (int(seed) + l * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+#: the index map of a Resample root (permutation rounds, with-replacement indices) draws under this key: the leaves own the
+#: multipliers 0 .. PLAN_MAX_LEAVES - 1, so no leaf shares it
+plan_index_seed = lambda seed: (int(seed) + PLAN_MAX_LEAVES * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
 
 
 def _plan_leaf(g):
@@ -826,8 +845,38 @@ def plan_spec(g):
     Concat inside Mesh / Ensemble, Mesh inside Ensemble, Ensemble inside Mesh, a mesh factor of more than one row (the
     reference makes every row an axis and gets ``size`` wrong), ensemble members of different sizes, segments with
     different row counts, more than six rows, more than eight leaves, 'latin-hypercube', and every other wrapper
-    (Transform / Filter / Resample / Batch / Sampler generators)."""
+    (Transform / Filter / Sampler generators; Resample / Batch anywhere but at the root).
+
+    At the ROOT only, drawn by ``ndq_sample_plan_indexed`` (still one launch, ``PlanSpec.index`` set)::
+
+        root      := Batch[resampled] | resampled
+        resampled := Resample[plan] | plan
+
+    ``BatchGenerator(inner, bs)``: draw ``t`` is the window ``[t * bs, (t + 1) * bs)`` of the concatenated stream of inner draws
+    (the reference's FIFO cache: the draw its constructor makes is inner draw 0, and a batch may straddle inner draws), so
+    ``BatchGenerator(ResampleGenerator(g), bs)`` is a shuffled epoch over ``g`` served ``bs`` points at a time.
+    ``ResampleGenerator(plan, size, replacement)``: element ``r`` of inner draw ``k`` is plan point ``j(r)`` of the plan's draw
+    ``k`` -- ``replacement=False``: the head of a random permutation of the plan's points (a swap-or-not shuffle evaluated per
+    index), ``True``: independent uniform indices -- under ``plan_index_seed(seed)``.  ``ValueError`` naming the node for
+    ``Resample[Batch[...]]``, two Resamples, two Batches, ``replacement=False`` with ``size > generator.size`` (the reference then
+    yields ``generator.size`` points, not ``size``), ``size < 1`` and a ``generator.size`` that is not the plan's point count."""
     wrappers, leaves, segments = [], [], []
+    batch, resample = None, None
+    if isinstance(g, BatchGenerator):
+        batch, g = g, g.generator
+        wrappers.append(batch)
+        if isinstance(g, BatchGenerator):
+            raise ValueError(f"BatchGenerator inside BatchGenerator is outside the plan sampler's normal form: {g!r} in {batch!r}")
+        if not isinstance(batch.size, (int, np.integer)) or not 1 <= batch.size <= 2 ** 31 - 1:
+            raise ValueError(f"{batch!r} has batch size {batch.size!r}: the device sampler serves 1 .. 2^31 - 1 points per draw")
+    if isinstance(g, ResampleGenerator):
+        resample, g = g, g.generator
+        wrappers.append(resample)
+        if isinstance(g, (ResampleGenerator, BatchGenerator)):
+            raise ValueError(f"{type(g).__name__} inside ResampleGenerator is outside the plan sampler's normal form: "
+                             f"{g!r} in {resample!r}")
+        if not isinstance(resample.size, (int, np.integer)) or not 1 <= resample.size <= 2 ** 31 - 1:
+            raise ValueError(f"{resample!r} has size {resample.size!r}: the device sampler draws 1 .. 2^31 - 1 points")
 
     def parts(node):                                   # Concat inside Concat: flattened
         if isinstance(node, ConcatGenerator):
@@ -887,7 +936,17 @@ def plan_spec(g):
         raise ValueError(f"{g!r} has {len(leaves)} leaves: the plan sampler takes at most {PLAN_MAX_LEAVES}")
     if offset > 2 ** 31 - 1:
         raise ValueError(f"{g!r} draws {offset} points: more than 2^31 - 1")
-    return PlanSpec(d, offset, leaves, segments, wrappers)
+    if batch is None and resample is None:
+        return PlanSpec(d, offset, leaves, segments, wrappers)
+    mode, m = "none", offset
+    if resample is not None:
+        if g.size != offset:
+            raise ValueError(f"{resample!r} draws its indices below generator.size = {g.size}, but the generator yields {offset} points")
+        mode, m = ("replace" if resample.replacement else "permute"), int(resample.size)
+        if mode == "permute" and m > offset:
+            raise ValueError(f"{resample!r} without replacement yields generator.size = {offset} points, not size = {m}: "
+                             "the device sampler draws blocks of a fixed size")
+    return PlanSpec(d, offset, leaves, segments, wrappers, index=PlanIndex(mode, offset, m, int(batch.size) if batch is not None else 0))
 
 
 # (N, 1) view lists handed out by DeviceGenerators -> the generator (engine.fast_train_epoch asks for a prefetch)
@@ -919,8 +978,13 @@ class DeviceGenerator(BaseGenerator):
     ``ndq_sample_plan``, no ``prefetch`` either): ``g1 + g2`` (ConcatGenerator), ``g1 * g2`` (EnsembleGenerator) and ``g1 ^ g2``
     (MeshGenerator) over any of the above, ``StaticGenerator`` and ``PredefinedGenerator`` (their fixed points, uploaded once and
     handed out bit for bit); leaf ``l`` of a composition draws under ``plan_leaf_seed(seed, l)``, so the batch is the
-    composition of what a DeviceGenerator of each leaf hands out under that seed.  Not drawn on the device: 'latin-hypercube' (a
-    permutation), alone or inside a wrapper, the Transform / Filter / Resample / Batch / Sampler generators, and compositions
+    composition of what a DeviceGenerator of each leaf hands out under that seed; and, at the ROOT of any of the above, by that
+    same launch (``ndq_sample_plan_indexed``): ``ResampleGenerator`` (with or without replacement) and ``BatchGenerator`` --
+    ``DeviceGenerator(BatchGenerator(ResampleGenerator(g), bs))`` is a shuffled epoch over ``g`` served ``bs`` points per draw
+    with no ``randperm``, gather or upload; draw ``t`` is the window ``[t * bs, (t + 1) * bs)`` of the stream of inner draws, the
+    permutation is a swap-or-not shuffle under ``plan_index_seed(seed)`` evaluated per point.  Opt-in: :func:`on_default_device`
+    never wraps these.  Not drawn on the device: 'latin-hypercube' (a permutation), alone or inside a wrapper, the
+    Transform / Filter / Sampler generators, Resample / Batch below the root, and compositions
     outside the normal form of :func:`plan_spec`.  ``get_examples`` enqueues
     one kernel on the current stream and returns ``(N, 1)`` views of ONE resident SoA block which the fused engine
     reads in place; the block is overwritten by the next draw (stream-ordered, so the previous step has consumed it).
@@ -1081,6 +1145,12 @@ class DeviceGenerator(BaseGenerator):
             g = d.seg[k]
             g.mode, g.first, g.count, g.offset, g.size = modes[mode], first, count, offset, size
         self.plan, self._table_buf, self.desc = plan, buf, d
+        self._index = None               # the ndq_plan_index_desc of a Resample / Batch root (ndq_sample_plan_indexed), else None
+        if plan.index is not None:
+            ix = _lib.PlanIndexDesc()
+            ix.mode = {"none": _lib.NDQ_INDEX_NONE, "permute": _lib.NDQ_INDEX_PERMUTE, "replace": _lib.NDQ_INDEX_REPLACE}[plan.index.mode]
+            ix.m, ix.batch = plan.index.m, plan.index.batch
+            self._index = ix
 
     def get_examples(self):
         if torch._C._len_torch_function_stack():          # a global default-device mode: see engine.library_code
@@ -1108,7 +1178,8 @@ class DeviceGenerator(BaseGenerator):
         # (DATA leaves: `examples` / `xs`), by identity; their lists and tensors join the element / version checks above
         self._quick_tree = ()
         if self.plan is not None:
-            watched = [(w, ("generators",)) for w in self.plan.wrappers] + [(f.gen, f.live) for f in self.plan.leaves]
+            watched = [(w, _LIVE_INDEX if isinstance(w, (ResampleGenerator, BatchGenerator)) else ("generators",))
+                       for w in self.plan.wrappers] + [(f.gen, f.live) for f in self.plan.leaves]
             tree = tuple((vars(o), n, vars(o).get(n), type(o), type(o).get_examples) for o, names in watched for n in names if n in vars(o))
             values = [e[2] for e in tree]
             lists = tuple((v, tuple(v)) for v in values if isinstance(v, (list, tuple)))
@@ -1209,7 +1280,12 @@ class DeviceGenerator(BaseGenerator):
             sample = self._L.ndq_sample if self.table is None else self._L.ndq_sample_table
             if self.plan is not None:
                 sample = self._L.ndq_sample_plan
-            rc = sample(ctypes.byref(self.desc), self.seed, self.draw, self.stream_id, block.data_ptr(), block.shape[1], stream)
+            if self.plan is not None and self._index is not None:
+                sample = self._L.ndq_sample_plan_indexed
+                rc = sample(ctypes.byref(self.desc), ctypes.byref(self._index), self.seed, self.draw, self.stream_id, block.data_ptr(),
+                            block.shape[1], stream)
+            else:
+                rc = sample(ctypes.byref(self.desc), self.seed, self.draw, self.stream_id, block.data_ptr(), block.shape[1], stream)
             if rc != 0:
                 from . import _lib
                 raise _lib.NdqError(f"{sample.__name__} failed with code {rc}")
