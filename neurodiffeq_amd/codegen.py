@@ -165,6 +165,37 @@ _UN_ADJ = {
 }
 
 
+def _forward_lines(g, order, val, symbols=()):
+    """The forward half of a traced DAG as straight-line fp32 statements, one ``const float v<i>`` per node of ``order`` (children
+    first).  val(i): the C expression of node i's value; symbols: the network symbols in use (``s[k]``), in order."""
+    L = []
+    for i in order:
+        n = g.nodes[i]
+        op = n[0]
+        if op in ("const", "coord", "data", "param"):
+            continue
+        if op == "net":
+            L.append(f"  const float v{i} = s[{symbols.index(i)}];")
+            continue
+        if op in ("add", "sub", "mul", "div"):
+            sym = {"add": "+", "sub": "-", "mul": "*", "div": "/"}[op]
+            e = f"{val(n[1])} {sym} {val(n[2])}"
+        elif op == "powi":
+            e = _powi_expr(val(n[1]), n[2])
+        elif op == "powc":
+            e = f"powf({val(n[1])}, {_lit(n[2])})"
+        elif op == "atan2":
+            e = f"atan2f({val(n[1])}, {val(n[2])})"
+        elif op in ("gt", "ge"):          # masks: 1.0f / 0.0f
+            e = f"(({val(n[1])} {'>' if op == 'gt' else '>='} {val(n[2])}) ? 1.0f : 0.0f)"
+        elif op == "where":               # a select, not a blend (symbolic.BINARY)
+            e = f"(({val(n[1])} != 0.0f) ? {val(n[2])} : {val(n[3])})"
+        else:
+            e = _UN_FWD[op].format(a=val(n[1]))
+        L.append(f"  const float v{i} = {e};")
+    return L
+
+
 def _closure_host(K, threads, points, slots, kern, kern_tv, lds, kern_loop=None, lds_loop=None):
     """Tail of a generated closure module: the traits struct ``Closure`` (what differs between the closure kernels; the
     contract is the file comment of csrc/ndq_closure_host.h), then that header -- the launchers and every ndq_fused_* export.
@@ -326,30 +357,7 @@ class PointwiseProgram:
         res_order = g.reachable(self.residuals)
         res_set = set(res_order)
         L.append("// ---- forward")
-        for i in self.order:
-            n = g.nodes[i]
-            op = n[0]
-            if op in ("const", "coord", "data", "param"):
-                continue
-            if op == "net":
-                L.append(f"  const float v{i} = s[{self.symbols.index(i)}];")
-                continue
-            if op in ("add", "sub", "mul", "div"):
-                sym = {"add": "+", "sub": "-", "mul": "*", "div": "/"}[op]
-                e = f"{self._val(n[1])} {sym} {self._val(n[2])}"
-            elif op == "powi":
-                e = _powi_expr(self._val(n[1]), n[2])
-            elif op == "powc":
-                e = f"powf({self._val(n[1])}, {_lit(n[2])})"
-            elif op == "atan2":
-                e = f"atan2f({self._val(n[1])}, {self._val(n[2])})"
-            elif op in ("gt", "ge"):          # masks: 1.0f / 0.0f
-                e = f"(({self._val(n[1])} {'>' if op == 'gt' else '>='} {self._val(n[2])}) ? 1.0f : 0.0f)"
-            elif op == "where":               # a select, not a blend (symbolic.BINARY)
-                e = f"(({self._val(n[1])} != 0.0f) ? {self._val(n[2])} : {self._val(n[3])})"
-            else:
-                e = _UN_FWD[op].format(a=self._val(n[1]))
-            L.append(f"  const float v{i} = {e};")
+        L += _forward_lines(g, self.order, self._val, self.symbols)
         for e, i in enumerate(self.residuals):
             L.append(f"  r[{e}] = {self._val(i)};")
         if self.loss == "custom":
@@ -858,6 +866,14 @@ def _build_tag():
     return _hipcc.FIXUP_VERSION if _hipcc.fixup_enabled() else "no-fixup"
 
 
+def _sampler_digest():
+    h = hashlib.sha1()
+    for name in ("csrc/ndq_sample.h", "csrc/ndq_sample_map.h"):
+        with open(os.path.join(HERE, name), "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
 def _header_digest():
     h = hashlib.sha1()
     for name in ("csrc/ndq_mlp.h", "csrc/ndq_tail.h", "csrc/ndq_launch.h", "csrc/ndq_wide.h", "csrc/ndq_deep.h", "csrc/ndq_closure_host.h",
@@ -865,6 +881,154 @@ def _header_digest():
         with open(os.path.join(HERE, name), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()
+
+
+# ----------------------------------------------------------------------------------------------- sampler stages
+MAP_MAX_ROWS = 6        # include/ndq.h NDQ_TABLE_MAX_AXES: rows of a plan point, rows a map may hand out
+#: the user's arithmetic as written: no mul + add -> fma (a mask `x*x + y*y < 1` sees the products torch sees; + - * /, comparisons
+#: and `where` are then torch's fp32 bit for bit).  The host build takes it as a flag.  The device build takes it as
+#: `#pragma clang fp contract(off)` in front of ndq_map_point only: as a hipcc FLAG it also changes how the backend expands logf
+#: inside the leaf laws of csrc/ndq_sample.h (a separate add instead of the last fused multiply-add), and a point recomputed by
+#: the module would then differ by an ulp from the point sample_plan_kernel stores for the same (seed, draw, stream, i)
+MAP_HOST_FLAGS = ["-ffp-contract=off"]
+
+
+class SamplerMapProgram:
+    """The traced stages of a device-drawn generator (generators.trace_stages: the callables of TransformGenerator /
+    FilterGenerator above a plan) lowered to straight-line fp32: the forward half of a :class:`PointwiseProgram` only -- no network
+    symbols, no adjoint, no data columns.  ``outs``: node ids of the rows handed out; ``keep``: node id of the AND of the filters'
+    masks, or None; ``d_in``: rows of a plan point.  ``source`` is ONE text for both build targets: hipcc (the kernels and the
+    launcher of csrc/ndq_sample_map.h, :func:`build_sampler_map`) and a host compiler (:func:`build_sampler_map_cpu`: the same
+    ``ndq_map_point`` behind a loop over points, for tests without a GPU)."""
+
+    def __init__(self, graph: Graph, outs, keep, d_in):
+        self.g, self.outs, self.keep, self.d_in, self.d_out = graph, list(outs), keep, int(d_in), len(outs)
+        if not 1 <= self.d_out <= MAP_MAX_ROWS or not 1 <= self.d_in <= MAP_MAX_ROWS:
+            raise ValueError(f"a sampler map takes and hands out 1 .. {MAP_MAX_ROWS} rows, not {self.d_in} -> {self.d_out}")
+        self.order = graph.reachable(self.outs + ([keep] if keep is not None else []))
+        for i in self.order:
+            n = graph.nodes[i]
+            if n[0] in ("net", "param", "data") or (n[0] == "coord" and n[1] >= self.d_in):
+                raise TraceUnsupported(f"a sampler stage may read the rows of its point and numbers only, not a {n[0]!r} leaf")
+        self.source = self._emit()
+        self.key = _cache_key(self.source + _sampler_digest())
+
+    def _val(self, i):
+        n = self.g.nodes[i]
+        return _lit(n[1]) if n[0] == "const" else (f"c{n[1]}" if n[0] == "coord" else f"v{i}")
+
+    def point_fn_source(self):
+        used = sorted({self.g.nodes[i][1] for i in self.order if self.g.nodes[i][0] == "coord"})
+        L = [f"  const float c{c} = v[{c}];" for c in used]
+        L += _forward_lines(self.g, self.order, self._val)
+        L += [f"  v[{r}] = {self._val(i)};" for r, i in enumerate(self.outs)]
+        L.append(f"  keep = {self._val(self.keep)} != 0.0f;" if self.keep is not None else "  keep = true;")
+        return ("NDQ_MAP_INLINE void ndq_map_point(float (&v)[6], bool& keep) {\n" + "\n".join(L) + "\n}\n")
+
+    def _emit(self):
+        return f"""// GENERATED by neurodiffeq_amd/codegen.py -- the per-point stages (TransformGenerator / FilterGenerator callables) of one
+// device-drawn generator: {self.d_in} row(s) of a plan point in, {self.d_out} row(s) out{', a keep mask' if self.keep is not None else ''}.
+#define NDQ_MAP_DIN {self.d_in}
+#define NDQ_MAP_DOUT {self.d_out}
+#define NDQ_MAP_FILTER {int(self.keep is not None)}
+#ifdef __HIPCC__
+#include "ndq_sample.h"
+#define NDQ_MAP_INLINE __device__ __forceinline__
+#pragma clang fp contract(off)
+#else
+#include <math.h>
+#define NDQ_MAP_INLINE static inline
+#endif
+{self.point_fn_source()}
+#ifdef __HIPCC__
+#include "ndq_sample_map.h"
+#else
+// rows [NDQ_MAP_DIN][n] -> out [NDQ_MAP_DOUT][n], keep [n]: ndq_map_point at every point (host build, for tests)
+extern "C" void ndq_map_cpu(const float* rows, int n, float* out, unsigned char* keep) {{
+  for (int i = 0; i < n; ++i) {{
+    float v[6] = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
+    for (int c = 0; c < NDQ_MAP_DIN; ++c) v[c] = rows[(size_t)c * n + i];
+    bool k = true;
+    ndq_map_point(v, k);
+    for (int c = 0; c < NDQ_MAP_DOUT; ++c) out[(size_t)c * n + i] = v[c];
+    keep[i] = k ? 1 : 0;
+  }}
+}}
+#endif
+"""
+
+
+class SamplerMapKernel:
+    def __init__(self, so_path):
+        self.path = so_path
+        self.lib = ctypes.CDLL(so_path)
+        vp, ci, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong
+        self.lib.ndq_map_launch.restype = ci
+        self.lib.ndq_map_launch.argtypes = [vp, vp, u64, u64, ctypes.c_uint, vp, ci, ci, vp, ci, vp]
+        self.rows_in, self.rows_out = self.lib.ndq_map_rows_in(), self.lib.ndq_map_rows_out()
+        self.filters = bool(self.lib.ndq_map_filters())
+        self.launch = self.lib.ndq_map_launch
+
+
+def build_sampler_map(program: SamplerMapProgram, force=False):
+    """Compile the map / filter module of ``program`` for gfx950 (in-tree cache keyed by the generated source, the sampler headers
+    and the flags) and return the .so path."""
+    os.makedirs(JIT_DIR, exist_ok=True)
+    so = os.path.join(JIT_DIR, f"smap_{program.key}.so")
+    src = so[:-3] + ".hip"
+    if os.path.exists(so) and not force:
+        return so
+    with open(src, "w") as fh:
+        fh.write(program.source)
+    try:
+        _hipcc.compile_shared(src, so, _extra_flags(), defer=True)
+    except RuntimeError as e:
+        raise RuntimeError(f"hipcc failed for generated sampler map module {src}:\n{str(e)[-4000:]}") from e
+    return so
+
+
+_MAP_MODULES = {}
+
+
+def load_sampler_map(program: SamplerMapProgram):
+    k = _MAP_MODULES.get(program.key)
+    if k is None:
+        k = _MAP_MODULES[program.key] = SamplerMapKernel(build_sampler_map(program))
+    return k
+
+
+def build_sampler_map_cpu(program: SamplerMapProgram, force=False):
+    """The same source through the host C++ compiler (the ``#else`` branches): ``ndq_map_cpu`` runs ``ndq_map_point`` over a
+    batch of rows.  No GPU, no hipcc; no contraction, like ndq_map_point in the device build."""
+    os.makedirs(JIT_DIR, exist_ok=True)
+    so = os.path.join(JIT_DIR, f"smap_cpu_{program.key}.so")
+    if os.path.exists(so) and not force:
+        return so
+    src = so[:-3] + ".cpp"
+    with open(src, "w") as fh:
+        fh.write(program.source)
+    import subprocess
+    tmp = f"{so}.{os.getpid()}.tmp"
+    cxx = os.environ.get("CXX", "g++")
+    proc = subprocess.run([cxx, "-O2", "-std=c++17", "-fno-fast-math"] + MAP_HOST_FLAGS + ["-shared", "-fPIC", src, "-o", tmp],
+                          capture_output=True, text=True)
+    if proc.returncode != 0:
+        raise RuntimeError(f"{cxx} failed for generated sampler map module {src}:\n{proc.stderr[-4000:]}")
+    os.replace(tmp, so)
+    return so
+
+
+def run_sampler_map_cpu(program: SamplerMapProgram, rows):
+    """rows [d_in][n] fp32 -> (out [d_out][n] fp32, keep [n] bool) through the host build."""
+    import numpy as np
+    lib = ctypes.CDLL(build_sampler_map_cpu(program))
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(program.d_in, -1)
+    n = rows.shape[1]
+    out, keep = np.zeros((program.d_out, n), np.float32), np.zeros(n, np.uint8)
+    lib.ndq_map_cpu.restype = None
+    lib.ndq_map_cpu.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.ndq_map_cpu(rows.ctypes.data, n, out.ctypes.data, keep.ctypes.data)
+    return out, keep.astype(bool)
 
 
 # ----------------------------------------------------------------------------------------------- MLP kernel extensions

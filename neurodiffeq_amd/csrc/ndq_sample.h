@@ -267,6 +267,7 @@ struct PlanArgs {                  // by value: 8 x 240 + 40 bytes of the 4 KB k
   unsigned c1, c2, c3;
   float* coords;
   int ldc, total;
+  int d;                           // rows of the plan (every point has all of them)
 };
 static_assert(sizeof(PlanArgs) <= 2048, "PlanArgs is passed by value");
 
@@ -284,15 +285,19 @@ template <int MODE> struct PlanIndexPoint;                  // window + index ma
 __device__ __forceinline__ const PlanArgs& plan_args(const PlanArgs& a) { return a; }
 __device__ __forceinline__ const PlanArgs& plan_args(const PlanIndexArgs& a);
 
+// ---- THE per-point body of the plan sampler: the rows of output point i, in registers (sample_plan_kernel; the generated
+// map / filter kernels of csrc/ndq_sample_map.h recompute a point with it instead of storing it).  false: i is past the last
+// output point (v is then not meaningful).  No thread returns before the barrier of PlanIndexPoint<PERMUTE>::map, so a caller may
+// go on to a workgroup barrier of its own.  v[row0 + c] is written through selects on wave-uniform conditions (row0 / rows are
+// scalar loads from the kernarg segment): no runtime-indexed private array, no scratch.
 template <int MODE, class Args>
-__global__ void __launch_bounds__(256) sample_plan_kernel(Args args) {
+__device__ __forceinline__ bool plan_point(const Args& args, unsigned i, float (&v)[NDQ_TABLE_MAX_AXES]) {
   const PlanArgs& a = plan_args(args);
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;       // (unsigned: the last workgroup of a 2^31 - 1 point draw)
   unsigned pt = 0u, k1 = 0u, k2 = 0u;                       // indexed: plan point and draw counter words of output point i
   if constexpr (MODE == NDQ_INDEX_PLAIN) {
-    if (i >= (unsigned)a.total) return;
+    if (i >= (unsigned)a.total) return false;
   } else {
-    if (!PlanIndexPoint<MODE>::map(args, i, pt, k1, k2)) return;
+    if (!PlanIndexPoint<MODE>::map(args, i, pt, k1, k2)) return false;
   }
   for (int l = 0; l < a.n_leaves; ++l) {
     const PlanLeaf& L = a.leaf[l];
@@ -300,22 +305,37 @@ __global__ void __launch_bounds__(256) sample_plan_kernel(Args args) {
     if (rel >= L.size) continue;
     const int j = (int)(L.div ? rel / L.div % L.n : rel);
     const DrawKey k{L.k0, L.k1, MODE == NDQ_INDEX_PLAIN ? a.c1 : k1, MODE == NDQ_INDEX_PLAIN ? a.c2 : k2, a.c3};
-    float v[NDQ_TABLE_MAX_AXES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float w[NDQ_TABLE_MAX_AXES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (L.kind == NDQ_LEAF_SIMPLE) {
       float s[3] = {0.0f, 0.0f, 0.0f};
       simple_point(L.u.simple, L.noisy, k, j, s);
-      v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+      w[0] = s[0]; w[1] = s[1]; w[2] = s[2];
     } else if (L.kind == NDQ_LEAF_TABLE) {
-      table_point(L.u.table, L.noisy, k, j, v);
+      table_point(L.u.table, L.noisy, k, j, w);
     } else {
 #pragma unroll
       for (int c = 0; c < NDQ_TABLE_MAX_AXES; ++c)
-        if (c < L.rows) v[c] = L.u.data[c][j];
+        if (c < L.rows) w[c] = L.u.data[c][j];
     }
 #pragma unroll
-    for (int c = 0; c < NDQ_TABLE_MAX_AXES; ++c)
-      if (c < L.rows) a.coords[(size_t)(L.row0 + c) * a.ldc + i] = v[c];
+    for (int r = 0; r < NDQ_TABLE_MAX_AXES; ++r)
+#pragma unroll
+      for (int c = 0; c <= r; ++c)
+        if (c < L.rows && L.row0 + c == r) v[r] = w[c];
   }
+  return true;
+}
+
+template <int MODE, class Args>
+__global__ void __launch_bounds__(256) sample_plan_kernel(Args args) {
+  const PlanArgs& a = plan_args(args);
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;       // (unsigned: the last workgroup of a 2^31 - 1 point draw)
+  float v[NDQ_TABLE_MAX_AXES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (!plan_point<MODE>(args, i, v)) return;
+  // (fill_plan_args: the leaves of every segment cover the rows 0 .. d - 1, each once -- every point has all d rows)
+#pragma unroll
+  for (int c = 0; c < NDQ_TABLE_MAX_AXES; ++c)
+    if (c < a.d) a.coords[(size_t)c * a.ldc + i] = v[c];
 }
 
 // validated launch arguments of one plan draw; returns 0 or NDQ_EINVAL (nothing is launched on NDQ_EINVAL)
@@ -393,7 +413,7 @@ inline int fill_plan_args(PlanArgs& a, const ndq_plan_sampler_desc* p, unsigned 
   if (next_leaf != p->n_leaves || ldc < total) return NDQ_EINVAL;
   a.n_leaves = p->n_leaves;
   a.c1 = (unsigned)draw; a.c2 = (unsigned)(draw >> 32); a.c3 = stream_id;
-  a.coords = coords; a.ldc = ldc; a.total = (int)total;
+  a.coords = coords; a.ldc = ldc; a.total = (int)total; a.d = p->d;
   return 0;
 }
 
@@ -410,7 +430,7 @@ inline int launch_sample_plan(const ndq_plan_sampler_desc* p, unsigned long long
 // include/ndq.h: ndq_sample_plan_indexed.  ResampleGenerator / BatchGenerator directly above a plan: output point i is element
 // r of inner draw k (the window), r is mapped to the plan point j (the index map), and the plan's own per-point body runs
 // at j with k as the draw number.  Philox is counter-based, so nothing is drawn twice and nothing is gathered.
-struct PlanIndexArgs {             // by value: PlanArgs + 48 bytes
+struct PlanIndexArgs {             // by value: PlanArgs + 40 bytes
   PlanArgs p;                      // p.total = n, the points of the plan; p.c1 / p.c2 are not used (k replaces the draw number)
   unsigned long long k0;           // inner draw of output point 0
   unsigned r0, m, n, rounds;       // its element there; points of one inner draw; plan points; PERMUTE: 2 bitlen(n - 1) + 8

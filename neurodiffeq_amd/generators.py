@@ -70,6 +70,8 @@ _LIVE_TABLE = ("grid_r", "grid_std", "getter", "examples", "noise_std", "size", 
 #: what a ResampleGenerator / BatchGenerator above a plan reads when it draws (BatchGenerator.cached_xs is host state: the device
 #: draw has no cache, its window is a function of the draw number)
 _LIVE_INDEX = ("size", "replacement", "generator")
+#: ... and a TransformGenerator / FilterGenerator of the root chain (FilterGenerator.size is an OUTPUT of a draw: the kept count)
+_LIVE_STAGE = ("trans", "filter_fn", "update_size", "generator")
 
 
 def live_stamp(gen, names=_LIVE):
@@ -784,15 +786,24 @@ class PlanSpec:
     """Host-side description of a composed draw (``ndq_plan_sampler_desc`` minus the device pointers): ``leaves`` numbered
     depth-first from 0, ``segments`` = [(mode, first leaf, leaf count, point offset, points)] with mode 'leaf' / 'ensemble' /
     'mesh', ``d`` rows, ``size`` points handed out per draw, ``wrappers``: every Concat / Ensemble / Mesh node of the tree (and the
-    root-level Resample / Batch nodes), ``index``: None, or the :class:`PlanIndex` of a Resample / Batch root -- ``size`` is then
-    ``index.batch or index.m``, the plan's own points are ``index.n``."""
+    root-level Resample / Batch / Transform / Filter nodes), ``index``: None, or the :class:`PlanIndex` of a Resample / Batch root
+    -- ``size`` is then ``index.batch or index.m``, the plan's own points are ``index.n``.  ``stages``: the per-point stages of the
+    root chain from inner to outer, each ``('map', callable or list of callables)`` (a TransformGenerator's ``trans``) or
+    ``('filter', fn)``; ``stage_nodes``: the generators they belong to; ``d_out``: rows handed out (``d`` without stages);
+    ``filtered``: a filter is among the stages -- ``size`` is then the capacity of a draw, the kept count varies.  With stages:
+    ``trace`` = (Graph, out nodes, keep node or None) of :func:`trace_stages`, ``watch``: the ``_pystate.StateWatch`` of the
+    callables."""
 
-    def __init__(self, d, size, leaves, segments, wrappers, index=None):
+    def __init__(self, d, size, leaves, segments, wrappers, index=None, stages=(), stage_nodes=()):
         self.d, self.leaves, self.segments, self.wrappers, self.index = d, leaves, segments, wrappers, index
         self.size = size if index is None else (index.batch or index.m)
+        self.stages, self.stage_nodes, self.d_out = list(stages), list(stage_nodes), d
+        self.filtered = any(kind == "filter" for kind, _ in self.stages)
+        self.trace = self.watch = None
 
 
 PLAN_MAX_LEAVES = 8
+PLAN_MAX_ROWS = 6          # include/ndq.h NDQ_TABLE_MAX_AXES
 #: leaf l of a plan draws under this seed (leaf 0: ``seed`` itself); two leaves never share a Philox key
 plan_leaf_seed = lambda seed, l: (int(seed) + l * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
 #: the index map of a Resample root (permutation rounds, with-replacement indices) draws under this key: the leaves own the
@@ -828,7 +839,7 @@ def _plan_leaf(g):
     return PlanLeaf(g, "table", spec.d, int(np.prod(spec.n)), _LIVE_TABLE, table=spec)
 
 
-def plan_spec(g):
+def plan_spec(g, _redraw=False):
     """:class:`PlanSpec` of a composed generator the plan sampler (``ndq_sample_plan``) draws in one launch.  Normal form::
 
         plan    := Concat[segment, ...]                       (a lone segment is a plan of one segment)
@@ -845,7 +856,7 @@ def plan_spec(g):
     Concat inside Mesh / Ensemble, Mesh inside Ensemble, Ensemble inside Mesh, a mesh factor of more than one row (the
     reference makes every row an axis and gets ``size`` wrong), ensemble members of different sizes, segments with
     different row counts, more than six rows, more than eight leaves, 'latin-hypercube', and every other wrapper
-    (Transform / Filter / Sampler generators; Resample / Batch anywhere but at the root).
+    (the Sampler generator; Resample / Batch / Transform / Filter anywhere but in the root chain).
 
     At the ROOT only, drawn by ``ndq_sample_plan_indexed`` (still one launch, ``PlanSpec.index`` set)::
 
@@ -859,24 +870,67 @@ def plan_spec(g):
     ``k`` -- ``replacement=False``: the head of a random permutation of the plan's points (a swap-or-not shuffle evaluated per
     index), ``True``: independent uniform indices -- under ``plan_index_seed(seed)``.  ``ValueError`` naming the node for
     ``Resample[Batch[...]]``, two Resamples, two Batches, ``replacement=False`` with ``size > generator.size`` (the reference then
-    yields ``generator.size`` points, not ``size``), ``size < 1`` and a ``generator.size`` that is not the plan's point count."""
+    yields ``generator.size`` points, not ``size``), ``size < 1`` and a ``generator.size`` that is not the plan's point count.
+
+    Per-point STAGES in the root chain, drawn by a generated module (``codegen.SamplerMapProgram``, csrc/ndq_sample_map.h)::
+
+        root   := stage* over (Batch[resampled] | resampled)
+        stage  := Transform | Filter
+
+    A ``TransformGenerator`` may sit above the root or between Batch and Resample (a per-point map commutes with the window;
+    below a Resample it stays refused: put it one level up, the points are the same); several compose in nesting order and may
+    change the number of rows (1 .. 6).  A ``FilterGenerator`` sits above every Resample / Batch (its output size varies);
+    transforms and further filters may sit above it: masks AND together, a later stage sees the rows as transformed so far.
+    ``PlanSpec.stages`` / ``stage_nodes`` / ``d_out`` / ``filtered`` describe them, ``trace`` / ``watch`` are :func:`trace_stages`'
+    result and the ``_pystate.StateWatch`` of the callables; every stage node joins ``wrappers``.  ``ValueError`` naming the node
+    for a stage inside Concat / Ensemble / Mesh, a Filter below Resample / Batch, more than six output rows, a Filter whose
+    ``size`` is not what it wraps, ``update_size=False``, whatever :func:`trace_stages` refuses, and callables whose state cannot
+    be watched.  (``_redraw``: a DeviceGenerator re-plans a tree it has been drawing -- a Filter's ``size`` is then the last kept
+    count.)"""
     wrappers, leaves, segments = [], [], []
     batch, resample = None, None
-    if isinstance(g, BatchGenerator):
-        batch, g = g, g.generator
-        wrappers.append(batch)
-        if isinstance(g, BatchGenerator):
-            raise ValueError(f"BatchGenerator inside BatchGenerator is outside the plan sampler's normal form: {g!r} in {batch!r}")
-        if not isinstance(batch.size, (int, np.integer)) or not 1 <= batch.size <= 2 ** 31 - 1:
-            raise ValueError(f"{batch!r} has batch size {batch.size!r}: the device sampler serves 1 .. 2^31 - 1 points per draw")
-    if isinstance(g, ResampleGenerator):
-        resample, g = g, g.generator
-        wrappers.append(resample)
-        if isinstance(g, (ResampleGenerator, BatchGenerator)):
-            raise ValueError(f"{type(g).__name__} inside ResampleGenerator is outside the plan sampler's normal form: "
-                             f"{g!r} in {resample!r}")
-        if not isinstance(resample.size, (int, np.integer)) or not 1 <= resample.size <= 2 ** 31 - 1:
-            raise ValueError(f"{resample!r} has size {resample.size!r}: the device sampler draws 1 .. 2^31 - 1 points")
+    root, stages = g, []                                # (stages: outer to inner while the chain is walked)
+    while isinstance(g, (BatchGenerator, ResampleGenerator, TransformGenerator, FilterGenerator)):
+        node, g = g, g.generator
+        wrappers.append(node)
+        if isinstance(node, TransformGenerator):
+            if resample is not None:
+                raise ValueError(f"TransformGenerator inside ResampleGenerator stays outside the plan sampler's normal form: {node!r} in "
+                                 f"{resample!r} -- put it above the ResampleGenerator (a per-point map commutes with the index map: the "
+                                 "same points)")
+            stages.append((("map", node.trans), node))
+        elif isinstance(node, FilterGenerator):
+            if batch is not None or resample is not None:
+                raise ValueError(f"FilterGenerator below {type(resample or batch).__name__} is outside the plan sampler's normal form (the "
+                                 f"size of its draw varies, the index map is built for a fixed one): {node!r} in {resample or batch!r}")
+            if not node.update_size:
+                raise ValueError(f"{node!r} has update_size=False: the device hand-out always reports the number of points it kept "
+                                 "(its tensors have that length), so `size` cannot stay behind")
+            if not _redraw and node.size != g.size:
+                raise ValueError(f"{node!r} has size = {node.size!r}, but the generator it filters yields {g.size} points")
+            stages.append((("filter", node.filter_fn), node))
+        elif isinstance(node, BatchGenerator):
+            if resample is not None:
+                raise ValueError(f"BatchGenerator inside ResampleGenerator is outside the plan sampler's normal form: "
+                                 f"{node!r} in {resample!r}")
+            if batch is not None:
+                raise ValueError(f"BatchGenerator inside BatchGenerator is outside the plan sampler's normal form: {node!r} in {batch!r}")
+            batch = node
+            if not isinstance(batch.size, (int, np.integer)) or not 1 <= batch.size <= 2 ** 31 - 1:
+                raise ValueError(f"{batch!r} has batch size {batch.size!r}: the device sampler serves 1 .. 2^31 - 1 points per draw")
+        else:
+            if resample is not None:
+                raise ValueError(f"ResampleGenerator inside ResampleGenerator is outside the plan sampler's normal form: "
+                                 f"{node!r} in {resample!r}")
+            resample = node
+            if not isinstance(resample.size, (int, np.integer)) or not 1 <= resample.size <= 2 ** 31 - 1:
+                raise ValueError(f"{resample!r} has size {resample.size!r}: the device sampler draws 1 .. 2^31 - 1 points")
+    stages.reverse()
+
+    def no_stage(sub, node):                           # (stages inside Concat / Ensemble / Mesh: a later change)
+        if isinstance(sub, (TransformGenerator, FilterGenerator)):
+            raise ValueError(f"{type(sub).__name__} inside {type(node).__name__} is outside the plan sampler's normal form (per-point "
+                             f"stages sit in the root chain only): {sub!r} in {node!r}")
 
     def parts(node):                                   # Concat inside Concat: flattened
         if isinstance(node, ConcatGenerator):
@@ -884,6 +938,7 @@ def plan_spec(g):
             if not node.generators:
                 raise ValueError(f"{node!r} concatenates nothing")
             for sub in node.generators:
+                no_stage(sub, node)
                 yield from parts(sub)
         else:
             yield node
@@ -893,6 +948,7 @@ def plan_spec(g):
         if not node.generators:
             raise ValueError(f"{node!r} combines nothing")
         for sub in node.generators:
+            no_stage(sub, node)
             if isinstance(sub, kind):
                 yield from members(sub, kind, inside)
             elif isinstance(sub, (ConcatGenerator, EnsembleGenerator, MeshGenerator)):
@@ -936,21 +992,88 @@ def plan_spec(g):
         raise ValueError(f"{g!r} has {len(leaves)} leaves: the plan sampler takes at most {PLAN_MAX_LEAVES}")
     if offset > 2 ** 31 - 1:
         raise ValueError(f"{g!r} draws {offset} points: more than 2^31 - 1")
-    if batch is None and resample is None:
-        return PlanSpec(d, offset, leaves, segments, wrappers)
-    mode, m = "none", offset
-    if resample is not None:
-        if g.size != offset:
-            raise ValueError(f"{resample!r} draws its indices below generator.size = {g.size}, but the generator yields {offset} points")
-        mode, m = ("replace" if resample.replacement else "permute"), int(resample.size)
-        if mode == "permute" and m > offset:
-            raise ValueError(f"{resample!r} without replacement yields generator.size = {offset} points, not size = {m}: "
-                             "the device sampler draws blocks of a fixed size")
-    return PlanSpec(d, offset, leaves, segments, wrappers, index=PlanIndex(mode, offset, m, int(batch.size) if batch is not None else 0))
+    index = None
+    if batch is not None or resample is not None:
+        mode, m = "none", offset
+        if resample is not None:
+            if resample.generator.size != offset:
+                raise ValueError(f"{resample!r} draws its indices below generator.size = {resample.generator.size}, but the generator "
+                                 f"yields {offset} points")
+            mode, m = ("replace" if resample.replacement else "permute"), int(resample.size)
+            if mode == "permute" and m > offset:
+                raise ValueError(f"{resample!r} without replacement yields generator.size = {offset} points, not size = {m}: "
+                                 "the device sampler draws blocks of a fixed size")
+        index = PlanIndex(mode, offset, m, int(batch.size) if batch is not None else 0)
+    plan = PlanSpec(d, offset, leaves, segments, wrappers, index, [st for st, _ in stages], [node for _, node in stages])
+    if stages:
+        from . import _pystate
+        plan.trace = trace_stages(plan)
+        plan.d_out = len(plan.trace[1])
+        plan.watch = _pystate.StateWatch([f for _, fn in plan.stages for f in (fn if isinstance(fn, (list, tuple)) else [fn])])
+        if not plan.watch.complete:
+            raise ValueError(f"the callables of the stages of {root!r} read state that cannot be watched for changes "
+                             f"({'; '.join(plan.watch.incomplete)}): the device sampler would go on drawing a stale transform / filter")
+    return plan
+
+
+def trace_stages(plan):
+    """The stages of ``plan`` run ONCE on symbolic columns (:mod:`neurodiffeq_amd.symbolic`: one ``coord`` per plan row) ->
+    ``(Graph, out_nodes, keep_node | None)``: the rows handed out and the AND of the filters' masks as nodes of one DAG, which
+    ``codegen.SamplerMapProgram`` lowers to ``ndq_map_point``.  A map stage is called like ``TransformGenerator.get_examples``
+    calls it (one callable on all columns, or a list of callables column by column) and its outputs are the next stage's
+    columns; a filter stage receives the LIST of current columns and returns a mask.  Fails closed -- ``ValueError`` naming the
+    stage's generator for: anything the tracer cannot express, an output that is not a per-point column, more than six rows, a
+    map that returns a mask, a filter that does not, the batch size read into arithmetic."""
+    from . import symbolic
+    from .symbolic import Sym
+    g = symbolic.Graph(plan.d)
+    keep = None
+    with symbolic.trace_scope(g):
+        cols = [Sym(g, g.coord(c), leaf=True) for c in range(plan.d)]
+        for k, ((kind, fn), node) in enumerate(zip(plan.stages, plan.stage_nodes)):
+            where = f"stage {k} ({'transform' if kind == 'map' else 'filter'}) of the device draw, {node!r}"
+            try:
+                if kind == "filter":
+                    out = fn(list(cols))
+                elif callable(fn):
+                    out = fn(*cols)
+                else:                                  # (like the reference: zip stops at the shorter of the two)
+                    out = fn[0](cols[0]) if len(cols) == 1 else tuple(t(x) for t, x in zip(fn, cols))
+            except symbolic.TraceUnsupported as e:
+                raise ValueError(f"{where} cannot be traced: {e}") from None
+            except Exception as e:       # noqa: BLE001 -- user code that fails on symbolic columns: the host generator stays
+                raise ValueError(f"{where} cannot be traced: {type(e).__name__}: {e}") from None
+            if kind == "filter":
+                if not (isinstance(out, Sym) and out.isbool):
+                    raise ValueError(f"{where}: filter_fn must return a boolean mask of the points, not {type(out).__name__}")
+                keep = out if keep is None else (keep & out)
+                continue
+            out = [out] if isinstance(out, (Sym, torch.Tensor)) or not isinstance(out, (tuple, list)) else list(out)
+            for o in out:
+                if not isinstance(o, Sym):
+                    raise ValueError(f"{where}: every output must be a per-point column of the batch length, not {type(o).__name__}")
+                if o.isbool:
+                    raise ValueError(f"{where}: a transform returned a boolean mask where a column of coordinates is expected")
+            if not 1 <= len(out) <= PLAN_MAX_ROWS:
+                raise ValueError(f"{where} hands out {len(out)} rows: the device sampler writes 1 .. {PLAN_MAX_ROWS}")
+            cols = [o._plain() for o in out]
+    outs, keep = [c.i for c in cols], (keep.i if keep is not None else None)
+    for i in g.reachable(outs + ([keep] if keep is not None else [])):
+        if g.nodes[i][0] == "param":
+            raise ValueError(f"a stage of {plan.stage_nodes[-1]!r} reads the batch size (x.shape[0], len(x), x.numel()) into its "
+                             "arithmetic: the device draw evaluates one point at a time")
+        if g.nodes[i][0] in ("net", "data"):
+            raise ValueError(f"a stage of {plan.stage_nodes[-1]!r} reads something other than the rows of its point")
+    return g, outs, keep
 
 
 # (N, 1) view lists handed out by DeviceGenerators -> the generator (engine.fast_train_epoch asks for a prefetch)
 _DEVICE_SOURCES = {}
+
+
+def _forget_sources(ids):
+    for i in ids:
+        _DEVICE_SOURCES.pop(i, None)
 
 
 def device_source(batch):
@@ -983,8 +1106,13 @@ class DeviceGenerator(BaseGenerator):
     ``DeviceGenerator(BatchGenerator(ResampleGenerator(g), bs))`` is a shuffled epoch over ``g`` served ``bs`` points per draw
     with no ``randperm``, gather or upload; draw ``t`` is the window ``[t * bs, (t + 1) * bs)`` of the stream of inner draws, the
     permutation is a swap-or-not shuffle under ``plan_index_seed(seed)`` evaluated per point.  Opt-in: :func:`on_default_device`
-    never wraps these.  Not drawn on the device: 'latin-hypercube' (a permutation), alone or inside a wrapper, the
-    Transform / Filter / Sampler generators, Resample / Batch below the root, and compositions
+    never wraps these; and, above the root of any of the above, ``TransformGenerator`` and ``FilterGenerator`` (:func:`plan_spec`
+    "stages"): the user's callables are traced once, compiled into a small module and applied per point -- a transform in the
+    plan's single launch, a filter by three launches (count, scan, order-preserving compact) plus ONE 4-byte readback of the
+    kept count per draw, the only host synchronisation of any route (a batch's length is part of its tensors' shape); ``size``
+    and the wrapped FilterGenerator's ``size`` follow the kept count, the views of a filtered draw are built per draw.
+    Not drawn on the device: 'latin-hypercube' (a permutation), alone or inside a wrapper, the Sampler generator,
+    Transform / Filter / Resample / Batch outside the root chain, stages that cannot be traced or watched, and compositions
     outside the normal form of :func:`plan_spec`.  ``get_examples`` enqueues
     one kernel on the current stream and returns ``(N, 1)`` views of ONE resident SoA block which the fused engine
     reads in place; the block is overwritten by the next draw (stream-ordered, so the previous step has consumed it).
@@ -1035,24 +1163,33 @@ class DeviceGenerator(BaseGenerator):
         self._on_host = False
         self._L = _lib.lib()
         ld = (self.size + 63) // 64 * 64
+        # rows of the resident block / rows handed out: a plan with stages draws d rows per point and hands out d_out
+        rows, self._rows_out = (self.desc.d, self.desc.d) if self.plan is None else (max(self.plan.d, self.plan.d_out), self.plan.d_out)
         # prefetch=True: a solver on the single-launch native path lets the extra workgroups of its sums + tail kernel
         # draw the NEXT batch (ndq_fused_step.next_sampler) -- the sampler launch leaves the step.  The points are the
         # same (draw k is a function of (seed, k, stream_id) only).  Two blocks alternate (draw k lives in block k & 1), so
         # the tensors handed out for an epoch keep that epoch's points until the END of the following epoch.
         self.prefetch = bool(prefetch)
-        self.blocks = [torch.zeros(self.desc.d, ld, dtype=torch.float32, device=self.device) for _ in range(2 if self.prefetch else 1)]
+        self.blocks = [torch.zeros(rows, ld, dtype=torch.float32, device=self.device) for _ in range(2 if self.prefetch else 1)]
         self.dtype = dtype
         # fp64: the tensors handed out are views of double blocks the fp32 draws are copied into
         self._out_blocks = self.blocks if dtype == torch.float32 else [torch.zeros_like(b, dtype=dtype) for b in self.blocks]
-        self._views_all = [[blk[i, :self.size].reshape(-1, 1) for i in range(self.desc.d)] for blk in self._out_blocks]
+        self._views_all = [[blk[i, :self.size].reshape(-1, 1) for i in range(self._rows_out)] for blk in self._out_blocks]
         self.block, self._views = self.blocks[0], self._views_all[0]
         self.prefetched = None       # draw number already sitting in its block, drawn ahead by a tail kernel
         self.launches = 0            # sampler kernels this generator launched itself (diagnostics / tests)
+        self.readbacks = 0           # kept counts read back from the device (filter route: one per draw)
         # (weak: the registry must not keep a generator -- two device blocks -- alive after its solver is gone; the entries go
-        # with it, before the ids of its view lists can be reused)
+        # with it, before the ids of its view lists can be reused.  The filter route hands out a new list per draw -- its length
+        # is the kept count --: _filtered_views replaces the generator's entry, the registry does not grow)
+        self._source_ids = set()
+        weakref.finalize(self, _forget_sources, self._source_ids)
         for views in self._views_all:
-            _DEVICE_SOURCES[id(views)] = weakref.ref(self)
-            weakref.finalize(self, _DEVICE_SOURCES.pop, id(views), None)
+            self._register(views)
+
+    def _register(self, views):
+        _DEVICE_SOURCES[id(views)] = weakref.ref(self)
+        self._source_ids.add(id(views))
 
     @staticmethod
     def describe(g):
@@ -1151,6 +1288,14 @@ class DeviceGenerator(BaseGenerator):
             ix.mode = {"none": _lib.NDQ_INDEX_NONE, "permute": _lib.NDQ_INDEX_PERMUTE, "replace": _lib.NDQ_INDEX_REPLACE}[plan.index.mode]
             ix.m, ix.batch = plan.index.m, plan.index.batch
             self._index = ix
+        # stages (TransformGenerator / FilterGenerator in the root chain): the generated module that draws plan + stages
+        self._map = self._work = None
+        if plan.stages:
+            from . import codegen
+            graph, outs, keep = plan.trace
+            self._map = codegen.load_sampler_map(codegen.SamplerMapProgram(graph, outs, keep, plan.d))
+            if plan.filtered:        # [kept | per-workgroup counts -> offsets]: owned by the generator, rewritten by every draw
+                self._work = torch.zeros(1 + (plan.size + 255) // 256, dtype=torch.int32, device=self.device)
 
     def get_examples(self):
         if torch._C._len_torch_function_stack():          # a global default-device mode: see engine.library_code
@@ -1178,7 +1323,8 @@ class DeviceGenerator(BaseGenerator):
         # (DATA leaves: `examples` / `xs`), by identity; their lists and tensors join the element / version checks above
         self._quick_tree = ()
         if self.plan is not None:
-            watched = [(w, _LIVE_INDEX if isinstance(w, (ResampleGenerator, BatchGenerator)) else ("generators",))
+            watched = [(w, _LIVE_INDEX if isinstance(w, (ResampleGenerator, BatchGenerator)) else
+                        _LIVE_STAGE if isinstance(w, (TransformGenerator, FilterGenerator)) else ("generators",))
                        for w in self.plan.wrappers] + [(f.gen, f.live) for f in self.plan.leaves]
             tree = tuple((vars(o), n, vars(o).get(n), type(o), type(o).get_examples) for o, names in watched for n in names if n in vars(o))
             values = [e[2] for e in tree]
@@ -1209,6 +1355,8 @@ class DeviceGenerator(BaseGenerator):
         tensors replaced / edited in place, another getter, another size): the wrapped generator's own host draw from now on,
         copied into the resident block -- what the reference would train on."""
         g = self.generator
+        if self.plan is not None and self.plan.stages:
+            return self._stages_changed()
         if self.plan is not None:                # (no partial rebuilds on this route: any change anywhere in the tree)
             self._to_host()
             return self._restamp()
@@ -1227,6 +1375,27 @@ class DeviceGenerator(BaseGenerator):
             self.prefetched = None              # (a batch drawn ahead by a tail kernel used the old widths)
         else:
             self._to_host()
+        self._restamp()
+
+    MAX_STAGE_REBUILDS = 3
+
+    def _stages_changed(self):
+        """A plan with stages whose tree changed (``trans`` / ``filter_fn`` replaced, another wrapped generator) or whose callables
+        read Python state that moved (a captured radius: ``PlanSpec.watch``): plan, trace and build again -- one hipcc run unless the
+        generated source was built before -- as long as the block still fits; after MAX_STAGE_REBUILDS of them, or when the new tree
+        cannot be drawn on the device, the wrapped generator's own host draw from now on."""
+        self._rebuilds = getattr(self, "_rebuilds", 0) + 1
+        plan = None
+        if self._rebuilds <= self.MAX_STAGE_REBUILDS:
+            try:
+                plan = plan_spec(self.generator, _redraw=True)
+            except ValueError:
+                plan = None
+        if plan is None or not plan.stages or plan.size != self.plan.size or plan.d_out != self._rows_out \
+                or max(plan.d, plan.d_out) != self.block.shape[0]:
+            self._to_host()
+        else:
+            self._set_plan(plan)
         self._restamp()
 
     def _to_host(self):
@@ -1255,7 +1424,7 @@ class DeviceGenerator(BaseGenerator):
     def _host_examples(self):
         ex = self.generator.get_examples()
         ex = [ex] if isinstance(ex, torch.Tensor) else list(ex)
-        if len(ex) != self.desc.d or ex[0].numel() != self.size:
+        if len(ex) != self._rows_out or ex[0].numel() != self._views_all[0][0].shape[0]:
             self.size = ex[0].numel()
             return [e.detach().reshape(-1, 1).to(self.device, self.dtype) for e in ex]      # (another shape altogether: plain tensors)
         block, views = self._out_blocks[0], self._views_all[0]
@@ -1268,10 +1437,12 @@ class DeviceGenerator(BaseGenerator):
     def _get_examples(self):
         if self._on_host:
             return self._host_examples()
-        if not self._unchanged():
+        if not self._unchanged() or (self.plan is not None and self.plan.watch is not None and self.plan.watch.dirty()):
             self._wrapped_changed()
             if self._on_host:
                 return self._host_examples()
+        if self.plan is not None and self._map is not None:
+            return self._staged_examples()
         block = self.block_of(self.draw)
         if self.prefetched == self.draw:          # a tail kernel has drawn this batch already
             self.prefetched = None
@@ -1296,6 +1467,50 @@ class DeviceGenerator(BaseGenerator):
         views = self._views_all[slot]
         self.block, self._views = block, views
         self.draw += 1
+        return views
+
+    def _staged_examples(self):
+        """One draw of a plan with stages through its generated module (csrc/ndq_sample_map.h).  Transform only: ONE launch into
+        the fixed views.  With a filter: three stream-ordered launches (count, scan, compact), then the kept count is read back --
+        one 4-byte device-to-host copy on the compute stream per draw, the only host synchronisation of this route: a batch's
+        length is part of its tensors' shape.  The views of that draw are built here; ``size`` -- this generator's and the
+        outermost FilterGenerator's -- follows the kept count (the reference's ``update_size=True``)."""
+        block = self.blocks[0]
+        stream = ctypes.c_void_p(_raw_stream(self.device.index))
+        work = self._work
+        rc = self._map.launch(ctypes.addressof(self.desc), ctypes.addressof(self._index) if self._index is not None else None,
+                              self.seed, self.draw, self.stream_id, block.data_ptr(), block.shape[1], block.shape[0],
+                              work.data_ptr() if work is not None else None, work.numel() if work is not None else 0, stream)
+        if rc != 0:
+            from . import _lib
+            raise _lib.NdqError(f"ndq_map_launch failed with code {rc}")
+        self.launches += 3 if work is not None else 1
+        if self.dtype != torch.float32:
+            self._out_blocks[0].copy_(block)             # (stream-ordered behind the draw)
+        views = self._views_all[0]
+        if work is not None:
+            kept = int(work[0].item())
+            self.readbacks += 1
+            if kept != views[0].shape[0]:
+                views = self._filtered_views(kept)
+            self.size = kept
+            for node in reversed(self.plan.stage_nodes):
+                if isinstance(node, FilterGenerator):
+                    node.size = kept
+                    break
+        self.block, self._views = block, views
+        self.draw += 1
+        return views
+
+    def _filtered_views(self, kept):
+        """The (kept, 1) views of a filtered draw; they take the place of the previous list here and in the registry of
+        :func:`device_source`."""
+        _forget_sources(self._source_ids)
+        self._source_ids.clear()
+        out = self._out_blocks[0]
+        views = [out[i, :kept].reshape(-1, 1) for i in range(self._rows_out)]
+        self._views_all = [views]
+        self._register(views)
         return views
 
     def _internal_vars(self):
