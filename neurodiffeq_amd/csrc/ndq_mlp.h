@@ -397,6 +397,9 @@ constexpr bool act_has_s4(int act) {
 #ifndef NDQ_KEEP_H
 #define NDQ_KEEP_H 1
 #endif
+#ifndef NDQ_REUSE_FWD
+#define NDQ_REUSE_FWD 1   // 8-wave closure builds of H = 32 networks (Cfg::REUSE_FWD); 0 = launder the layer states as before
+#endif
 #ifndef NDQ_FWD_THREADS
 #define NDQ_FWD_THREADS 256
 #endif
@@ -713,10 +716,8 @@ struct Cfg {
   static constexpr bool BF16O = BF16 && (NOUT_ > 1) && (NBO % 2 == 0);
   static constexpr int NCO = NBO / 2;
   static constexpr int WOEL = BF16O ? (HO * H * 3) / 2 : HO * H;   // floats of LDS per output-layer image
-  // (two-waves-per-SIMD builds have no registers to keep them in: they recompute, and tile_backward hides the layer states
-  // behind an opaque copy so that the compiler does not quietly keep the forward pass's values alive instead)
+  // (one wave per SIMD only; the source of the two-waves-per-SIMD builds recomputes them -- see LAUNDER below)
   static constexpr bool KEEP_H = (NB_ == 2) && (NDQ_KEEP_H != 0) && (SS::NS <= 6) && (BWD_THREADS == 256);
-  static constexpr bool LAUNDER = ((NB_ == 2) && (BWD_THREADS != 256)) || (NB_ >= 4 && NDQ_WIDE_LAUNDER);
   // wide nets (H >= 64): the reverse pass is register-bound, so (a) the per-point GEMMs go through their bf16 planes
   // SG streams at a time instead of all at once, (b) the bias-type gradient sums (db_l, dW1, dWout: one value per
   // unit) live in a per-wave LDS region instead of registers, (c) the first layer's derivative streams (columns of
@@ -780,6 +781,25 @@ struct Cfg {
   static constexpr bool WG_TR64 = WG32 && (NOUT_ == 1) && (NDQ_WG_TR != 0) && (NDQ_WG_TR_K == 1) &&
                                   (ldsWeightsEnd(true) + (BWD_THREADS / 64) * (trStage64 + biasFloats) + 64 <= 40 * 1024);
   static constexpr int stageFloatsPerWave = WG_TR ? trStage : WG_TR64 ? trStage64 : stageFloatsPlain;
+  // LAUNDER: the source of the two-waves-per-SIMD builds (256 registers per wave) recomputes in the reverse pass what it
+  // needs of the forward pass, and tile_backward hides the layer states behind an opaque copy so that the compiler does
+  // not quietly keep the forward pass's values alive instead -- when that build was made, keeping them cost spills.
+  // REUSE_FWD, the single-network H = 32 closure kernels on the WG_TR route: no opaque copy.  Their reverse pass reads the
+  // inner layers' planes back from LDS, the training kernel is at 230 of 256 registers, and what is recomputed -- the last
+  // hidden layer's streams for dWout, s1, s2 and sum z_a^2 in act_backward -- is 117 of 1 010 VALU instructions per tile
+  // (C2).  Without the copy these are common subexpressions of act_forward's and the compiler keeps them: 236 registers,
+  // no scratch.  (Keeping them in the source as well -- KeptPlanes for the last layer, a struct of factors handed to
+  // act_backward -- compiles to the same instructions, so the source stays as it was.)
+  static constexpr bool REUSE_FWD = (NB_ == 2) && (BWD_THREADS != 256) && WG_TR && (NDQ_WG_TR_K == 1) && (ACTP_ == 0) &&
+                                    (SS::NS <= 6) && (NDQ_F64 == 0) && (NDQ_REUSE_FWD != 0);
+  static constexpr bool LAUNDER = ((NB_ == 2) && (BWD_THREADS != 256) && !REUSE_FWD) || (NB_ >= 4 && NDQ_WIDE_LAUNDER);
+};
+// Cfg with REUSE_FWD taken back (fused_closure_loop_kernel: its 8-wave build is over the register file as it is -- 256
+// registers, 216 B of scratch -- and everything the compiler keeps in addition is spilled)
+template <class C>
+struct RecomputeCfg : C {
+  static constexpr bool REUSE_FWD = false;
+  static constexpr bool LAUNDER = C::LAUNDER || C::REUSE_FWD;
 };
 
 struct MlpArgs {
@@ -2535,7 +2555,8 @@ __device__ __forceinline__ void tile_backward(const real* lds, real* stage, int 
                                               const real (&x)[C::D], const real (&gout)[C::NS],
                                               LayerState<C> (&st)[C::L], GradAcc<C>& acc, KeptPlanes<C>& kp) {
   // ---------------- output layer adjoint (n_out = 1): hbar = Wout * gout; dWout += sum_s gout_s h_s; dbout += gout_0
-  // (h_s of the last hidden layer is recomputed per stream from its state instead of being kept live)
+  // (h_s of the last hidden layer is recomputed per stream from its state instead of being kept live -- in the source;
+  // without LAUNDER the compiler may reuse the forward pass's values, see Cfg::REUSE_FWD)
   if constexpr (C::LAUNDER) {
 #pragma unroll
     for (int l = 0; l < C::L; ++l)
@@ -3238,7 +3259,7 @@ __global__ __launch_bounds__(C::BWD_THREADS) void fused_closure_loop_kernel(Fuse
       FusedArgs a = t;
       a.coords = t.coords + (size_t)e * (size_t)L.coord_stride;
       a.params = state; a.partials = state + 3 * PP; a.loss_partials = misc;
-      fused_closure_body<C, PW, true>(a, lds, 0, 1, none, false);
+      fused_closure_body<RecomputeCfg<C>, PW, true>(a, lds, 0, 1, none, false);
       __syncthreads();
     }
   }
