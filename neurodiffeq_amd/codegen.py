@@ -489,6 +489,8 @@ NDQ_PW_INLINE float ndq_pw_loss(const float* r) {{ return {term}; }}
         assert mode is not None and not (f64 and (mode != "tile" or K != 1))
         if mode in ("group", "wide"):
             return self._group_source(desc, wide=(mode == "wide"))
+        if mode == "wide_multi":
+            return self._group_source(desc, wide=True, nets=K)
         ns = self.streams[0].n_streams
         nsym = max(len(self.symbols), 1)
         jet = (lambda k, loc: f"jets[{loc}]") if K == 1 else (lambda k, loc: f"jets[{k}][{loc}]")
@@ -558,26 +560,30 @@ struct PW {{
 }};
 {host}"""
 
-    def _group_source(self, desc, wide=False):
+    def _group_source(self, desc, wide=False, nets=1):
         """Source of the grouped single-launch closure kernel (csrc/ndq_mlp.h: fused_group_closure_kernel): one network
         with any number of outputs, reading any subset of the batch coordinates; the per-point function runs on one
         point per lane, stream values and adjoint seeds are exchanged through an LDS tile.
         ``wide``: the closure kernel of csrc/ndq_wide.h (one hidden layer of 65 .. 512 units) -- the same per-point
-        interface, stream rows [n_streams][n_out] without padding."""
+        interface, stream rows [n_streams][n_out] without padding.
+        ``nets`` = K > 1 (with ``wide``): wide_multi_closure_kernel, K networks of ONE WideCfg behind one launch -- the same
+        per-point interface with the K rows side by side, [net][n_streams][n_out]."""
         st = self.streams[0]
         width = st.n_streams * st.n_out
+        assert nets == 1 or (wide and all(self.streams[k].n_streams * self.streams[k].n_out == width for k in range(nets)))
         gw = 1 if st.n_out == 1 else (st.n_out + 15) // 16 * 16      # row layout [n_streams][gw] (ndq::group_w)
         if wide:
             gw = st.n_out
-        row = lambda loc: (loc // st.n_out) * gw + loc % st.n_out
+        row = lambda k, loc: k * width + (loc // st.n_out) * gw + loc % st.n_out
         nsym = max(len(self.symbols), 1)
         used = {}
         loads = []
         for idx, i in enumerate(self.symbols):
             k, loc = self.sym_location(i)
-            used[loc] = idx
-            loads.append(f"    s[{idx}] = srow[{row(loc)}];")
-        stores = [f"    grow[{row(loc)}] = {'g[%d]' % used[loc] if loc in used else '0.0f'};" for loc in range(width)]
+            used[(k, loc)] = idx
+            loads.append(f"    s[{idx}] = srow[{row(k, loc)}];")
+        stores = [f"    grow[{row(k, loc)}] = {'g[%d]' % used[(k, loc)] if (k, loc) in used else '0.0f'};"
+                  for k in range(nets) for loc in range(width)]
         deps = list(st.deps)
         dep_fn = " : ".join(f"d == {d} ? {c}" for d, c in enumerate(deps)) + " : 0"
         header = "ndq_mlp.h"                 # found through -I csrc (_hipcc.BASE_FLAGS): sources and cache keys do not depend on the checkout path
@@ -592,9 +598,13 @@ struct PW {{
             lds = lambda train: "(ndq::wide_closure_lds_bytes<CFG, PW>())"
             kern_tv = "ndq::wide_closure_tv_kernel<CFG, PW>"
             cfg_t, points = wide_cfg(desc), 16
-        host = _closure_host(1, "CFG::BWD_THREADS", points, "CFG::BWD_THREADS / 64", kern, kern_tv, lds)
+        if nets > 1:
+            kern = lambda train: f"ndq::wide_multi_closure_kernel<CFG, {nets}, PW, {train}>"
+            lds = lambda train: f"(ndq::wide_multi_closure_lds_bytes<CFG, {nets}, PW>())"
+            kern_tv = f"ndq::wide_multi_closure_tv_kernel<CFG, {nets}, PW>"
+        host = _closure_host(nets, "CFG::BWD_THREADS", points, "CFG::BWD_THREADS / 64", kern, kern_tv, lds)
         return f"""// GENERATED by neurodiffeq_amd/codegen.py -- grouped single-launch closure kernel (forward streams -> LDS exchange ->
-// per-point stage, one point per lane -> reverse pass) of one PDE system, gfx950.
+// per-point stage, one point per lane -> reverse pass) of one PDE system{f" with {nets} networks" if nets > 1 else ""}, gfx950.
 {CLOSURE_PRODUCTS}#include "{header}"
 #define NDQ_PW_INLINE __device__ __forceinline__
 #ifndef NDQ_MAX_BLOCKS
@@ -1253,6 +1263,9 @@ def fuse_mode(program: PointwiseProgram, descs=None):
     "group"  one network with several outputs and / or reading only some of the batch coordinates, H <= 48
              (fused_group_closure_kernel: per-point stage on one point per lane through an LDS exchange tile);
              NDQ_FUSE_GROUP=1 sends every eligible single-network system there.
+    "wide"   one network with ONE hidden layer of 65 .. 512 units (csrc/ndq_wide.h: wide_closure_kernel),
+    "wide_multi"  2..4 such networks of one shape, stream set and input coordinates (wide_multi_closure_kernel);
+             NDQ_NO_WIDE_MULTI_FUSE is its off-switch.
     None     three-kernel pipeline."""
     K = program.n_nets
     if K < 1 or K > 4 or program.n_sites != K or any(k not in program.streams for k in range(K)):
@@ -1272,6 +1285,12 @@ def fuse_mode(program: PointwiseProgram, descs=None):
         if plain and not (group_ok and os.environ.get("NDQ_FUSE_GROUP") == "1"):
             return "tile"
         return "group" if group_ok else None
+    if descs is not None and all(k in descs for k in range(K)) and any(is_wide(descs[k]) for k in range(K)):
+        d0, deps = descs[0], tuple(program.streams[0].deps)
+        ok = (len({descs[k].key() for k in range(K)}) == 1 and d0.layers == 1 and not (d0.skip or d0.actp or d0.mono)
+              and all(c < program.n_coords for c in deps) and all(tuple(program.streams[k].deps) == deps for k in range(K))
+              and not os.environ.get("NDQ_NO_WIDE_MULTI_FUSE"))
+        return "wide_multi" if ok else None
     if not plain:
         return None
     if descs is None or len({descs[k].key() for k in range(K)}) != 1 or padded_width(descs[0].hidden) > 48:

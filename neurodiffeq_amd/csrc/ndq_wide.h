@@ -672,4 +672,239 @@ __global__ __launch_bounds__(C::THREADS) void wide_closure_tv_kernel(FusedArgs t
   else wide_closure_body<C, PW, false>(v, lds, (int)blockIdx.x - train_blocks, (int)gridDim.x - train_blocks);
 }
 
+// ------------------------------------------------------------------------------------------------ K networks, single launch
+// Systems with one network per unknown (solvers.py:136-140), every network the same WideCfg: the tile loop of wide_closure_body
+// with K forward passes, ONE per-point stage on all K stream rows and K reverse passes.  What a wave keeps where:
+//   gradient accumulators  registers, all K networks (they are sums over the wave's points: K x U (D + 1 + NOUT) values);
+//   a network's units      NOT resident: wave k builds network k's WideUnits once per workgroup and leaves them in LDS as an
+//                          image [field][unit lane]; every pass over a tile re-reads the image of its network (consecutive
+//                          lanes read consecutive words, the point lanes of a unit lane the same word: no bank conflict) --
+//                          the register budget is that of the one-network kernel plus (K - 1) accumulator sets, whatever K;
+//   kept sigma states      registers; all K networks' states between the forward and the reverse half where K sets are at most
+//                          128 values (KEEP_ALL), else network by network from a second, output-free forward pass just before
+//                          its reverse pass (the activation is evaluated twice; no stream is recomputed).
+// Per-wave LDS (floats): reduction rows | K output slices [16][NCP] | K seed slices [16][NCP].  wide_tile_forward addresses its
+// rows and its output block from ONE base; network k gets the base (K - 1 - k) slices up, so that its output block lands in
+// slice k (counted from the top) while its reduction rows overlay only reduction rows and slices no earlier network wrote.
+template <class C, int K>
+struct WideMulti {
+  static_assert(K >= 2 && K <= kMaxFusedNets, "2 .. 4 networks of one shape");
+  static constexpr int NXP = C::NX > 0 ? C::NX : 1;
+  static constexpr int FIELDS = C::U * (C::D + 1 + NXP + C::NOUT + (C::NOUT == 1 ? C::NS : 0));   // floats of a lane's WideUnits
+  static constexpr int IMG = FIELDS * C::UL;                                                   // ... of a network's image
+  static constexpr int SLICE = 16 * C::NCP;
+  static constexpr int fwd_base(int k) { return (K - 1 - k) * SLICE; }                         // handed to wide_tile_forward
+  static constexpr int out(int k) { return fwd_base(k) + C::ldsOut; }                          // network k's stream rows
+  static constexpr int seed(int k) { return C::ldsOut + (K + k) * SLICE; }                     // network k's adjoint seeds
+  static constexpr int bwd_base(int k) { return seed(k) - C::ldsSeed; }                        // handed to wide_tile_backward
+  static constexpr int waveFloats = (C::ldsOut + 2 * K * SLICE + 3) & ~3;
+  static constexpr bool KEEP_ALL = K * C::ROUNDS * C::U * 2 <= 128;
+  static constexpr int redFloats = (C::P + 16 + 3) & ~3;                                       // wide_block_reduce_store's rows
+};
+
+template <class C>
+__device__ __forceinline__ void wide_units_to_image(const WideUnits<C>& un, real* img, int ul) {
+  int f = 0;
+  auto put = [&](real v) { img[(f++) * C::UL + ul] = v; };
+#pragma unroll
+  for (int i = 0; i < C::U; ++i) {
+#pragma unroll
+    for (int a = 0; a < C::D; ++a) put(un.w[i][a]);
+    put(un.b[i]);
+#pragma unroll
+    for (int x = 0; x < (C::NX > 0 ? C::NX : 1); ++x) put(C::NX > 0 ? un.cs[i][x] : 0.f);
+#pragma unroll
+    for (int o = 0; o < C::NOUT; ++o) put(un.wo[i][o]);
+    if constexpr (C::NOUT == 1) {
+#pragma unroll
+      for (int s = 0; s < C::NS; ++s) put(un.k[i][s]);
+    }
+  }
+}
+
+template <class C>
+__device__ __forceinline__ void wide_units_from_image(const real* img, int ul, WideUnits<C>& un) {
+  int f = 0;
+  auto get = [&]() { return img[(f++) * C::UL + ul]; };
+#pragma unroll
+  for (int i = 0; i < C::U; ++i) {
+#pragma unroll
+    for (int a = 0; a < C::D; ++a) un.w[i][a] = get();
+    un.b[i] = get();
+#pragma unroll
+    for (int x = 0; x < (C::NX > 0 ? C::NX : 1); ++x) un.cs[i][x] = get();
+#pragma unroll
+    for (int o = 0; o < C::NOUT; ++o) un.wo[i][o] = get();
+    if constexpr (C::NOUT == 1) {
+#pragma unroll
+      for (int s = 0; s < C::NS; ++s) un.k[i][s] = get();
+    }
+  }
+}
+
+// PW (generated, codegen.py): the per-point interface of wide_closure_body with the K networks' rows side by side --
+// srow / grow [net][stream][out], K * C::NC values, the order fused_multi_closure_kernel hands its jets[K][NS].
+template <class C, int K, class PW, bool TRAIN>
+__device__ __forceinline__ void wide_multi_closure_body(const FusedMultiArgs& a, real* lds, const int blk, const int nblk) {
+  using M = WideMulti<C, K>;
+  static_assert(C::WAVES >= K, "wave k stages network k's image");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = lane & 15, q = lane >> 4;
+  const int ul = lane & (C::UL - 1), pl = lane / C::UL;
+  real* work = lds + K * M::IMG;               // behind the images: the waves' tile regions, later the reduction rows
+  real* wl = work + wave * M::waveFloats;
+  // coordinates one tile ahead, as wide_closure_body (the first tile's load overlaps the staging of the images)
+  const int ntiles = (a.n + 15) >> 4;
+  real ccn[PW::NC];
+  {
+    const int n0 = (blk * C::WAVES + wave) * 16 + p;
+    const int nn0 = n0 < a.n ? n0 : a.n - 1;
+#pragma unroll
+    for (int d = 0; d < PW::NC; ++d) ccn[d] = a.coords[(size_t)d * a.ldc + nn0];
+  }
+  sfor<K>([&](auto k_) {
+    constexpr int k = decltype(k_)::value;
+    if (wave == k) {
+      WideUnits<C> un;
+      wide_load_units<C>(a.params[k], ul, un);
+      if (pl == 0) wide_units_to_image<C>(un, lds + k * M::IMG, ul);
+    }
+  });
+  __syncthreads();
+  WideGrad<C> g[K];
+  real gbo[K][C::NOUT];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if constexpr (TRAIN) wide_grad_zero<C>(g[k]);
+#pragma unroll
+    for (int o = 0; o < C::NOUT; ++o) gbo[k][o] = 0.f;
+  }
+  real lsum = 0.f;
+  real th[PW::NT > 0 ? PW::NT : 1], tsum[PW::NT > 0 ? PW::NT : 1];
+#pragma unroll
+  for (int j = 0; j < PW::NT; ++j) { th[j] = a.theta[j]; tsum[j] = 0.f; }
+  for (int tile = blk * C::WAVES + wave; tile < ntiles; tile += nblk * C::WAVES) {
+    const int n = tile * 16 + p;
+    const bool valid = n < a.n;
+    real cc[PW::NC];
+#pragma unroll
+    for (int d = 0; d < PW::NC; ++d) cc[d] = ccn[d];
+    {
+      const int n1 = n + nblk * C::WAVES * 16;
+      const int nn1 = n1 < a.n ? n1 : a.n - 1;
+#pragma unroll
+      for (int d = 0; d < PW::NC; ++d) ccn[d] = a.coords[(size_t)d * a.ldc + nn1];
+    }
+    real xv[C::D];
+    sfor<C::D>([&](auto d_) {
+      constexpr int d = decltype(d_)::value;
+      xv[d] = cc[PW::dep(d)];
+    });
+    WideKept<C> kept[M::KEEP_ALL ? K : 1];
+    // ---- K forward passes: network k's stream rows -> slice k
+    sfor<K>([&](auto k_) {
+      constexpr int k = decltype(k_)::value;
+      WideUnits<C> un;
+      wide_units_from_image<C>(lds + k * M::IMG, ul, un);
+      wide_tile_forward<C, TRAIN && M::KEEP_ALL, true>(un, xv, wl + M::fwd_base(k), a.params[k] + C::offbout, lane, ul, pl,
+                                                      kept[M::KEEP_ALL ? k : 0]);
+    });
+    // ---- per-point stage, once, on lanes 0 .. 15; seeds -> the K seed slices
+    if (q == 0) {
+      real r[PW::NR], f[PW::NF > 0 ? PW::NF : 1], gth[PW::NT > 0 ? PW::NT : 1];
+#pragma unroll
+      for (int j = 0; j < PW::NT; ++j) gth[j] = 0.f;
+      real srow[K * C::NC], grow[K * C::NC];
+      sfor<K>([&](auto k_) {
+        constexpr int k = decltype(k_)::value;
+#pragma unroll
+        for (int c = 0; c < C::NC; ++c) {
+          srow[k * C::NC + c] = wl[M::out(k) + p * C::NCP + c];
+          grow[k * C::NC + c] = 0.f;
+        }
+      });
+      PW::apply(cc, th, srow, valid ? a.seed : 0.f, TRAIN ? 1 : 0, r, f, grow, gth);
+      if constexpr (TRAIN) {
+        sfor<K>([&](auto k_) {
+          constexpr int k = decltype(k_)::value;
+#pragma unroll
+          for (int c = 0; c < C::NCP; ++c) wl[M::seed(k) + p * C::NCP + c] = c < C::NC ? grow[k * C::NC + (c < C::NC ? c : 0)] : 0.f;
+        });
+      }
+      if (valid) {
+        lsum += PW::loss(r);
+        if constexpr (TRAIN) {
+#pragma unroll
+          for (int j = 0; j < PW::NT; ++j) tsum[j] += gth[j];
+#pragma unroll
+          for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int o = 0; o < C::NOUT; ++o) gbo[k][o] += grow[k * C::NC + o];
+        }
+        if (a.resid) {
+#pragma unroll
+          for (int e = 0; e < PW::NEQ; ++e) a.resid[(size_t)e * a.ldj + n] = r[e];
+        }
+        if (a.funcs) {
+#pragma unroll
+          for (int m = 0; m < PW::NF; ++m) a.funcs[(size_t)m * a.ldj + n] = f[m];
+        }
+      }
+    }
+    // ---- K reverse passes
+    if constexpr (TRAIN) {
+      wave_lds_sync();
+      sfor<K>([&](auto k_) {
+        constexpr int k = decltype(k_)::value;
+        WideUnits<C> un;
+        wide_units_from_image<C>(lds + k * M::IMG, ul, un);
+        if constexpr (!M::KEEP_ALL) wide_tile_forward<C, true, false>(un, xv, wl, nullptr, lane, ul, pl, kept[0]);
+        wide_tile_backward<C>(un, xv, wl + M::bwd_base(k), pl, kept[M::KEEP_ALL ? k : 0], g[k]);
+      });
+    }
+    wave_lds_sync();
+  }
+  // per-network block partial rows, network by network through the same reduction rows (fixed order; the call begins with a
+  // workgroup barrier, so the previous network's rows have been read by then)
+  if constexpr (TRAIN) {
+    sfor<K>([&](auto k_) {
+      constexpr int k = decltype(k_)::value;
+      WideUnits<C> un;
+      wide_units_from_image<C>(lds + k * M::IMG, ul, un);
+      wide_block_reduce_store<C>(un, g[k], gbo[k], work, wave, lane, ul, pl, a.partials[k] + (size_t)blk * C::P);
+    });
+  }
+  lsum = point_sum(quad_sum(lsum));
+  __syncthreads();
+  real* ws = work + M::redFloats;
+  if (lane == 0) ws[wave] = lsum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    real v = 0.f;
+    for (int w = 0; w < C::WAVES; ++w) v += ws[w];
+    a.loss_partials[blk] = v;
+  }
+  if constexpr (TRAIN) theta_block_sum<PW::NT>(tsum, ws + 16, C::WAVES, a.theta_partials ? a.theta_partials + (size_t)blk * PW::NT : nullptr);
+}
+
+template <class C, int K, class PW> constexpr size_t wide_multi_closure_lds_bytes() {
+  using M = WideMulti<C, K>;
+  const int tiles = C::WAVES * M::waveFloats;
+  const int red = M::redFloats + 32 + C::WAVES * (PW::NT > 0 ? PW::NT : 1);
+  return sizeof(real) * (K * M::IMG + (tiles > red ? tiles : red));
+}
+
+template <class C, int K, class PW, bool TRAIN>
+__global__ __launch_bounds__(C::THREADS) void wide_multi_closure_kernel(FusedMultiArgs a) {
+  extern __shared__ __attribute__((aligned(16))) real lds[];
+  wide_multi_closure_body<C, K, PW, TRAIN>(a, lds, blockIdx.x, gridDim.x);
+}
+
+// training batch and validation batch in one launch, as wide_closure_tv_kernel
+template <class C, int K, class PW>
+__global__ __launch_bounds__(C::THREADS) void wide_multi_closure_tv_kernel(FusedMultiArgs t, FusedMultiArgs v, int train_blocks, PullArgs) {
+  extern __shared__ __attribute__((aligned(16))) real lds[];
+  if ((int)blockIdx.x < train_blocks) wide_multi_closure_body<C, K, PW, true>(t, lds, blockIdx.x, train_blocks);
+  else wide_multi_closure_body<C, K, PW, false>(v, lds, (int)blockIdx.x - train_blocks, (int)gridDim.x - train_blocks);
+}
+
 }  // namespace ndq

@@ -526,6 +526,8 @@ class FusedSystem:
         mode = codegen.fuse_mode(self.program, self.descs)
         if mode == "multi":
             return False            # K x G waves, one per SIMD, whatever the batch size (csrc/ndq_mlp.h: multi_threads)
+        if mode == "wide_multi":
+            return False            # one wave per SIMD holds K networks' accumulators (csrc/ndq_wide.h: NDQ_WIDE_THREADS)
         if mode == "group":
             return os.environ.get("NDQ_GROUP_WIDE", "0") == "1"     # experiment: 8 waves with 32-point groups
         d = self.descs[0]
@@ -987,8 +989,8 @@ class FusedSystem:
         return ok
 
     def fused_closure(self, b, n, stream, train, n_global, slot, accumulate, want_funcs=False, want_resid=False):
-        """The whole closure in ONE launch (one network, or 2..4 networks of one shape), then the fixed-order
-        second-stage sums."""
+        """The whole closure in ONE launch (one network, or 2..4 networks of one shape -- up to 48 units, or one hidden layer
+        of 65 .. 512), then the fixed-order second-stage sums, network by network."""
         for fp in self.flat:
             fp.sync()
         seed = 1.0 / (float(n_global) * self.loss_norm)
