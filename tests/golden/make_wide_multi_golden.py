@@ -21,7 +21,7 @@ _spec.loader.exec_module(WM)
 
 def config(name):
     system, width = WM.GOLDEN[name]
-    kind, K, d_in = WM.SYSTEMS[system]
+    kind, K, d_in = WM.SYSTEMS[system][:3]
 
     def build():
         nets = [MG.FCNN(d_in, 1, hidden_units=(width,)) for _ in range(K)]

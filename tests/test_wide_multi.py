@@ -33,9 +33,14 @@ def traced(nets, conds, eqs, n_coords):
     return engine.trace_system(nets, conds, eqs, n_coords)
 
 
-def system(name, width):
+def system(name, width, act=None):
     torch.manual_seed(0)
-    return traced(*WM.make(name, width))
+    return traced(*WM.make(name, width, act))
+
+
+#: the cases of the GPU matrix beyond lv / uvp / four: third-order streams, mixed second derivatives on sigmoid / swish / GELU
+#: networks, trainable scalars in the equations, and the system that does not fit one workgroup's LDS
+NEW_CASES = [c for c in WM.GPU_CASES if c[0] in ("ode3", "mix", "mix4", "lvtheta")]
 
 
 def _exports(so):
@@ -152,6 +157,48 @@ def test_module_size_is_what_the_layout_says_and_decides_whether_the_engine_keep
     assert fits == (want <= 160 * 1024)
     if (name, width) == ("four", 512):
         assert fits, "four 512-unit networks of one input: 12 KiB of unit image each, 91 KiB in all"
+
+
+@pytest.mark.parametrize("case", NEW_CASES, ids=WM.case_id)
+def test_new_systems_take_the_wide_multi_closure_with_one_descriptor(case):
+    """Third-order streams, mixed second derivatives, sigmoid / swish / GELU, trainable scalars: all inside the family, every
+    network of a system on ONE descriptor (stream set unified over the networks)."""
+    name, K, d_in = case[0], WM.SYSTEMS[case[0]][1], WM.SYSTEMS[case[0]][2]
+    program, descs = system(*case)
+    assert program.n_nets == K and len({descs[k].key() for k in range(K)}) == 1
+    assert codegen.fuse_mode(program, descs) == "wide_multi" and codegen.can_fuse(program, descs)
+    d = descs[0]
+    want = {"ode3": (1, 1, 1, 0), "mix": (1, 7, 0, 0), "mix4": (1, 7, 0, 0), "lvtheta": (1, 0, 0, 0)}[name]
+    assert (d.first, d.mask2, d.mask3, d.lap) == want and d.d == d_in and d.hidden == case[1] and d.layers == 1
+    assert d.act == {"tanh": 0, "sin": 1, "sigmoid": 2, "swish": 3, "gelu": 7}[WM.activation(case)]
+    assert _lib.lib().ndq_mlp_num_streams(ctypes.byref(d)) == WM.n_streams(name)
+    assert len(program.g.params) == (2 if name == "lvtheta" else 0) and not program.g.frozen
+
+
+def test_layout_restatement_at_the_sizes_worked_out_by_hand():
+    assert wide_multi_lds_bytes(2, 512, 4, 3) == 131072          # uvp 512
+    assert wide_multi_lds_bytes(2, 512, 4, 4) == 151552          # a uvp-shaped system of four: still inside
+    assert wide_multi_lds_bytes(2, 200, 6, 2) == 86784           # mix 200
+    assert wide_multi_lds_bytes(2, 512, 6, 4) == 175104          # mix4 512: outside
+    assert 151552 <= 160 * 1024 < 175104
+
+
+@pytest.mark.parametrize("case", [c for c in WM.GPU_CASES if c[:2] not in (("lv", 80), ("uvp", 128), ("four", 72), ("four", 512))],
+                         ids=WM.case_id)
+def test_module_size_of_every_gpu_case_and_which_ones_the_engine_keeps(case):
+    """ndq_fused_lds_bytes() of every module the GPU matrix launches is what the layout says -- trainable scalars (their block
+    sums behind the reduction rows) included --, and exactly the case listed as over the budget exceeds 160 KiB."""
+    name, width = case[:2]
+    K, d_in = WM.SYSTEMS[name][1:3]
+    program, descs = system(*case)
+    lib = _load(codegen.build_fused(program, descs[0]))
+    n_theta = len(program.g.params)
+    assert n_theta == (2 if name == "lvtheta" else 0) and lib.ndq_fused_num_theta() == n_theta
+    want = wide_multi_lds_bytes(d_in, width, WM.n_streams(name), K, n_theta=n_theta)
+    assert lib.ndq_fused_lds_bytes() == want and lib.ndq_fused_num_nets() == K
+    assert (want > 160 * 1024) == (case in WM.OVER_LDS)
+    assert lib.ndq_fused_threads() == 256 and lib.ndq_fused_blocks(16384) == 256 and lib.ndq_fused_blocks(16400) == 256
+    assert lib.ndq_fused_blocks(16368) == 256 and lib.ndq_fused_blocks(16320) == 255       # ceil(ceil(n / 16) / 4), at most 256
 
 
 def test_goldens_are_reproduced_by_the_fp64_oracle(golden_dir):
