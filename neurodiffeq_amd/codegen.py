@@ -196,15 +196,17 @@ def _forward_lines(g, order, val, symbols=()):
     return L
 
 
-def _closure_host(K, threads, points, slots, kern, kern_tv, lds, kern_loop=None, lds_loop=None):
+def _closure_host(K, threads, points, slots, kern, kern_tv, lds, kern_loop=None, lds_loop=None, sites=False):
     """Tail of a generated closure module: the traits struct ``Closure`` (what differs between the closure kernels; the
     contract is the file comment of csrc/ndq_closure_host.h), then that header -- the launchers and every ndq_fused_* export.
-    kern(train) / lds(train): C++ text of the plain kernel and of its LDS bytes; kern_loop=None: no loop-mode kernel."""
+    kern(train) / lds(train): C++ text of the plain kernel and of its LDS bytes; kern_loop=None: no loop-mode kernel.
+    sites: an evaluation-site module -- K parameter sets behind the multi-network argument struct (K = 1 included), no pull mode."""
+    no_pull = "\n  static constexpr bool NO_PULL = true;" if sites else ""
     return f"""struct Closure {{
   using Cfg = CFG;
   using Pw = PW;
-  using Args = ndq::{'FusedArgs' if K == 1 else 'FusedMultiArgs'};
-  static constexpr int K = {K}, THREADS = {threads}, POINTS = {points}, SLOTS = {slots};
+  using Args = ndq::{'FusedArgs' if K == 1 and not sites else 'FusedMultiArgs'};
+  static constexpr int K = {K}, THREADS = {threads}, POINTS = {points}, SLOTS = {slots};{no_pull}
   static constexpr auto train = &{kern('true')};
   static constexpr auto eval = &{kern('false')};
   static constexpr auto tv = &{kern_tv};
@@ -483,14 +485,38 @@ NDQ_PW_INLINE float ndq_pw_loss(const float* r) {{ return {term}; }}
             return "#define NDQ_F64 1\n" + source_f64(self._fused_source(desc, True))
         return self._fused_source(desc, False)
 
+    def _site_traits(self):
+        """The traits struct of an evaluation-site module (csrc/ndq_mlp.h: SiteIdentity is the contract): which network wave
+        group k runs, whether it is that network's first site (rank 0: its waves write the gradient row), and which of its
+        inputs are boundary values."""
+        S, sn = self.n_sites, self.site_net
+        rank = [sn[:k].count(sn[k]) for k in range(S)]
+        virt = [[(d, self.g.vcoords[c]) for d, c in enumerate(self.streams[k].deps) if c in self.g.vcoords] for k in range(S)]
+        vmask = [sum(1 << d for d, _ in v) for v in virt]
+        chain = lambda vals, fmt: " : ".join([f"k == {k} ? {fmt(v)}" for k, v in enumerate(vals[:-1])] + [fmt(vals[-1])])
+        values = "".join(f"(k == {k} && d == {d}) ? {_lit(v)} : " for k in range(S) for d, v in virt[k]) + "0.0f"
+        lits = "; ".join(f"site {k} input {d} = {_lit(v)}" for k in range(S) for d, v in virt[k])
+        return f"""// evaluation sites: wave group k runs network NET[k] = {{{", ".join(map(str, sn))}}}
+// boundary values: {lits}
+struct SITES {{
+  static constexpr bool ON = true;
+  static constexpr int net(int k) {{ return {chain(sn, str)}; }}
+  static constexpr int rank(int k) {{ return {chain(rank, str)}; }}
+  static constexpr unsigned vmask(int k) {{ return {chain(vmask, lambda v: f"{v}u")}; }}
+  static constexpr float value(int k, int d) {{ return {values}; }}
+}};
+"""
+
     def _fused_source(self, desc, f64):
         K = self.n_nets
-        mode = fuse_mode(self, {k: desc for k in range(K)})
+        mode = fuse_mode(self, {k: desc for k in range(max(K, self.n_sites))})
         assert mode is not None and not (f64 and (mode != "tile" or K != 1))
         if mode in ("group", "wide"):
             return self._group_source(desc, wide=(mode == "wide"))
         if mode == "wide_multi":
             return self._group_source(desc, wide=True, nets=K)
+        if mode == "sites":
+            return self._site_source(desc)
         ns = self.streams[0].n_streams
         nsym = max(len(self.symbols), 1)
         jet = (lambda k, loc: f"jets[{loc}]") if K == 1 else (lambda k, loc: f"jets[{k}][{loc}]")
@@ -546,6 +572,62 @@ struct PW {{
   static __device__ __forceinline__ void apply(const float (&x)[CFG::D], const float* xe, {jets_t}, float seed,
                                                int want_adj, float (&r)[{self.n_r}], float (&f)[{max(nf, 1)}],
                                                {gj_t}, float* gth) {{
+    float c[CFG::D + ND + NT], s[{nsym}], g[{nsym} + NT];
+#pragma unroll
+    for (int d = 0; d < CFG::D; ++d) c[d] = x[d];
+#pragma unroll
+    for (int j = 0; j < ND + NT; ++j) c[CFG::D + j] = xe[j];
+{chr(10).join(loads)}
+    ndq_pw_point(c, s, seed, want_adj, r, f, g);
+{chr(10).join(stores)}
+#pragma unroll
+    for (int j = 0; j < NT; ++j) gth[j] = g[{len(self.symbols)} + j];
+  }}
+}};
+{host}"""
+
+    def _site_source(self, desc):
+        """The multi-network closure kernel for a system with evaluation sites (Neumann ends): S = 2..4 sites of fewer
+        networks on S wave groups.  Stream arrays are per site, parameter sets and gradient partials per network."""
+        S, ns = self.n_sites, self.streams[0].n_streams
+        nsym = max(len(self.symbols), 1)
+        loads, stores, used = [], [], {}
+        for idx, i in enumerate(self.symbols):
+            k, loc = self.sym_location(i)
+            used[(k, loc)] = idx
+            loads.append(f"    s[{idx}] = jets[{k}][{loc}];")
+        for k in range(S):
+            for loc in range(ns):
+                stores.append(f"    gj[{k}][{loc}] = {'g[%d]' % used[(k, loc)] if (k, loc) in used else '0.0f'};")
+        neq, nf = len(self.residuals), len(self.funcs)
+        kern = lambda train: f"ndq::fused_multi_closure_kernel<CFG, {S}, PW, {train}, SITES>"
+        lds = lambda train: f"(ndq::fused_multi_lds_bytes<CFG, {S}>({train}))"
+        host = _closure_host(self.n_nets, f"ndq::multi_threads<{S}>()", 16, f"ndq::multi_group<{S}>()", kern,
+                             f"ndq::fused_multi_closure_tv_kernel<CFG, {S}, PW, SITES>", lds, sites=True)
+        # (NDQ_WG_TR_K: weight images in LDS -- one per site, a network with two sites is staged twice.)  No CLOSURE_PRODUCTS:
+        # every GEMM keeps all six bf16 plane products.  A network's gradient is the SUM of its sites' and those nearly cancel
+        # (u - u(x_b) - w u_x(x_b): the output bias drops out exactly), so the 4- / 3-product reverse and weight-gradient
+        # GEMMs of the other closure modules, 1e-6 of each site's gradient, come to 1e-5 of the network's (measured: heat
+        # equation with two Neumann ends 1.25e-5 against fp64 with them, 2e-7 without); these systems are launch-bound
+        wg_tr = f"#ifndef NDQ_WG_TR\n#define NDQ_WG_TR 1\n#endif\n#define NDQ_WG_TR_K {S}\n"
+        return f"""// GENERATED by neurodiffeq_amd/codegen.py -- single-launch closure kernel (forward streams + pointwise stage +
+// reverse pass) of one PDE system with {self.n_nets} network(s) at {S} evaluation sites, gfx950.
+{wg_tr}#include "ndq_mlp.h"
+#define NDQ_PW_INLINE __device__ __forceinline__
+#ifndef NDQ_MAX_BLOCKS
+#define NDQ_MAX_BLOCKS 256     // closure workgroups per launch (one per CU)
+#endif
+{self.point_fn_source()}
+namespace {{
+using CFG = {mlp_cfg(desc, 1)};
+{self._site_traits()}struct PW {{
+  // ND per-point data columns (rows D .. D + ND of the coordinate block), NT trainable scalars of the equations
+  static constexpr int NEQ = {neq}, NF = {nf}, NR = {self.n_r}, ND = {self.n_data}, NT = {self.n_theta};
+  static __device__ __forceinline__ float loss(const float* r) {{ return ndq_pw_loss(r); }}
+  // x: the batch point (every site's real inputs);  jets / gj: streams and their adjoints, per SITE
+  static __device__ __forceinline__ void apply(const float (&x)[CFG::D], const float* xe, const float (&jets)[{S}][CFG::NS],
+                                               float seed, int want_adj, float (&r)[{self.n_r}], float (&f)[{max(nf, 1)}],
+                                               float (&gj)[{S}][CFG::NS], float* gth) {{
     float c[CFG::D + ND + NT], s[{nsym}], g[{nsym} + NT];
 #pragma unroll
     for (int d = 0; d < CFG::D; ++d) c[d] = x[d];
@@ -1266,8 +1348,14 @@ def fuse_mode(program: PointwiseProgram, descs=None):
     "wide"   one network with ONE hidden layer of 65 .. 512 units (csrc/ndq_wide.h: wide_closure_kernel),
     "wide_multi"  2..4 such networks of one shape, stream set and input coordinates (wide_multi_closure_kernel);
              NDQ_NO_WIDE_MULTI_FUSE is its off-switch.
+    "sites"  networks evaluated on a boundary as well (Neumann ends): 2..4 evaluation sites of fewer networks, all of one
+             shape and stream set, one output, H <= 48, fp32, no third- / fourth-order streams; every site reads all batch
+             coordinates, some of them replaced by a boundary value (fused_multi_closure_kernel with site traits, one wave
+             group per site); NDQ_NO_SITE_FUSE is its off-switch.
     None     three-kernel pipeline."""
     K = program.n_nets
+    if K >= 1 and program.n_sites > K:
+        return "sites" if _sites_ok(program, descs) else None
     if K < 1 or K > 4 or program.n_sites != K or any(k not in program.streams for k in range(K)):
         return None
     plain = all(tuple(program.streams[k].deps) == tuple(range(program.n_coords)) and program.streams[k].n_out == 1
@@ -1298,6 +1386,25 @@ def fuse_mode(program: PointwiseProgram, descs=None):
     if os.environ.get("NDQ_NO_MULTI_FUSE"):
         return None
     return "multi"
+
+
+def _sites_ok(program, descs):
+    """``fuse_mode``: may the evaluation-site closure kernel serve this system?"""
+    S, nc = program.n_sites, program.n_coords
+    if not (2 <= S <= 4) or os.environ.get("NDQ_NO_SITE_FUSE") or any(k not in program.streams for k in range(S)):
+        return False
+    if descs is None or any(k not in descs for k in range(S)) or len({descs[k].key() for k in range(S)}) != 1:
+        return False
+    d0 = descs[0]
+    if is_wide(d0) or padded_width(d0.hidden) > 48 or d0.n_out != 1 or d0.mask3 or getattr(d0, "mask4", 0):
+        return False
+    for k in range(S):               # (fp64 systems never get here with a say: can_fuse_f64 takes "tile" only)
+        st = program.streams[k]
+        if st.n_out != 1 or st.mask3 or getattr(st, "mask4", 0) or len(st.deps) != nc:
+            return False
+        if any(c != a and c not in program.g.vcoords for a, c in enumerate(st.deps)):
+            return False              # entry a of a site's inputs: batch coordinate a, or a boundary value
+    return True
 
 
 def can_fuse(program: PointwiseProgram, descs=None):

@@ -17,6 +17,7 @@
 //   train, eval, tv             kernel entry points (constexpr pointers): training closure, forward-only closure,
 //                               training + validation closure;  LDS_TRAIN, LDS_EVAL their dynamic LDS bytes
 //   loop, LDS_LOOP              the loop-mode kernel and its LDS bytes, or `nullptr` and 0 where there is none
+//   NO_PULL                     optional; true: the kernels have no pull prologue whatever the Cfg (evaluation-site modules)
 #pragma once
 #include <cstdlib>
 #include <type_traits>
@@ -41,6 +42,11 @@ template <int K> void fill(ndq::FusedArgs& a, const ndq::real* const* params, nd
 template <int K> void fill(ndq::FusedMultiArgs& a, const ndq::real* const* params, ndq::real* const* partials) {
   for (int k = 0; k < K; ++k) { a.params[k] = params[k]; a.partials[k] = partials ? partials[k] : nullptr; }
 }
+
+// does the module's train + validation kernel carry the pull prologue (csrc/ndq_tail.h)?
+template <class T, class = void> struct no_pull : std::false_type {};
+template <class T> struct no_pull<T, std::void_t<decltype(T::NO_PULL)>> : std::bool_constant<T::NO_PULL> {};
+template <class T> constexpr bool pull_ok() { return ndq::pull_supported<typename T::Cfg>() && !no_pull<T>::value; }
 
 template <class T>
 int launch(const ndq::real* coords, int ldc, int n, const ndq::real* const* params, ndq::real* const* partials,
@@ -102,7 +108,7 @@ int launch_tv(const ndq::real* coords, int ldc, int n, const ndq::real* const* p
   }
   ndq::PullArgs pa{};        // pull prologue (csrc/ndq_tail.h): the launch finishes the previous epoch itself
   if (pull) {
-    if (!ndq::pull_supported<typename T::Cfg>()) return -2;
+    if (!pull_ok<T>()) return -2;
     pa = *static_cast<const ndq::PullArgs*>(pull);
   }
   hipLaunchKernelGGL(T::tv, dim3(tb + vb), dim3(T::THREADS), tb > 0 ? T::LDS_TRAIN : T::LDS_EVAL,
@@ -119,7 +125,7 @@ int launch_loop(const ndq::real* coords, int ldc, int n, ndq::real seed, const n
   if constexpr (!has_loop<T>()) {
     return -2;
   } else {
-    if (!loop || !ndq::pull_supported<typename T::Cfg>() || n < 0 || vn < 0 ||
+    if (!loop || !pull_ok<T>() || n < 0 || vn < 0 ||
         (n > 0 && (!coords || ldc < n || fused_blocks<T>(n) != 1)) ||
         (vn > 0 && (!vcoords || vldc < vn || fused_blocks<T>(vn) != 1)))
       return -2;
@@ -139,7 +145,7 @@ int launch_loop(const ndq::real* coords, int ldc, int n, ndq::real seed, const n
   }
 }
 template <class T> int loop_ok() {
-  return has_loop<T>() && ndq::pull_supported<typename T::Cfg>() && T::LDS_LOOP <= 160 * 1024 ? 1 : 0;
+  return has_loop<T>() && pull_ok<T>() && T::LDS_LOOP <= 160 * 1024 ? 1 : 0;
 }
 
 }  // namespace
@@ -190,7 +196,7 @@ extern "C" int ndq_fused_launch_tv(const ndq::real* coords, int ldc, int n, cons
                                    void* stream) {
   return launch_tv<Closure>(coords, ldc, n, params, partials, loss_partials, seed, vcoords, vldc, vn, vloss_partials, pull, stream);
 }
-extern "C" int ndq_fused_pull_ok() { return ndq::pull_supported<Closure::Cfg>() ? 1 : 0; }
+extern "C" int ndq_fused_pull_ok() { return pull_ok<Closure>() ? 1 : 0; }
 // the ndq_fused_launch_loop_fn of include/ndq.h
 extern "C" int ndq_fused_launch_loop(const ndq::real* coords, int ldc, int n, ndq::real seed, const ndq::real* vcoords,
                                      int vldc, int vn, const void* loop, void* stream) {

@@ -3315,7 +3315,26 @@ struct MultiLoopView {
   const real* coords; const real* params_base; real* partials_base; real* loss_partials; int stride;
 };
 
-template <class C, int K, class PW, bool TRAIN>
+// Evaluation sites.  A condition with a Neumann end evaluates its network on the boundary as well as at the batch point
+// (symbolic.Graph: a *site* = one network at one coordinate tuple, some of whose entries are constants).  To this kernel a
+// site is a "network" whose parameters may be those of another wave group and some of whose inputs are literals: wave group
+// k runs network net(k); input d of it is value(k, d) where bit d of vmask(k) is set, else the tile's coordinate d.  A
+// network's gradient is the sum over its sites, taken INSIDE the workgroup: every site's waves leave their sum in LDS (over
+// the site's weight image, which nobody reads any more), and the waves of the network's first site (rank(k) == 0) add the
+// sites in index order and write the workgroup's ONE row of that network's partials -- no atomics, no further launch, and the
+// sums / tail launch sees what it sees for K networks.  In the workgroup and not across rows of the partial buffers, because
+// site contributions cancel (u - u(x_b): the output bias drops out exactly, each workgroup's two sums being exact negatives);
+// summed row by row across workgroups the zero would become rounding noise, which Adam turns into steps of size lr.
+// The code generator emits the traits of a system (codegen.py: _site_traits); this is the identity -- K networks, one site each.
+struct SiteIdentity {
+  static constexpr bool ON = false;
+  static constexpr int net(int k) { return k; }
+  static constexpr int rank(int) { return 0; }
+  static constexpr unsigned vmask(int) { return 0u; }
+  static constexpr real value(int, int) { return 0; }
+};
+
+template <class C, int K, class PW, bool TRAIN, class ST = SiteIdentity>
 __device__ __forceinline__ void fused_multi_closure_body(const FusedMultiArgs& a, real* lds, const int blk, const int nblk,
                                                          const PullArgs& pull, bool writer, const MultiLoopView& lv) {
   static_assert(C::NOUT == 1 && !C::WIDE && K >= 2 && K <= kMaxFusedNets, "multi-network closure: n_out = 1, H <= 48, 2..4 nets");
@@ -3327,8 +3346,9 @@ __device__ __forceinline__ void fused_multi_closure_body(const FusedMultiArgs& a
   const int k = wave / G, g = wave - k * G;            // this wave's network and its tile slot in a round
   // loop mode hands in its LDS-resident buffers through `lv` (the argument struct itself stays in the kernarg segment)
   const real* const coords = lv.params_base ? lv.coords : a.coords;
-  const real* const prm_k = lv.params_base ? lv.params_base + k * lv.stride : a.params[k];
-  real* const part_k = lv.params_base ? lv.partials_base + k * lv.stride : a.partials[k];
+  const int net_k = ST::net(k);                        // (the identity unless the module was generated for evaluation sites)
+  const real* const prm_k = lv.params_base ? lv.params_base + k * lv.stride : a.params[net_k];
+  real* const part_k = lv.params_base ? lv.partials_base + k * lv.stride : a.partials[net_k];
   real* const lpart = lv.params_base ? lv.loss_partials : a.loss_partials;
   const int ntiles = (a.n + 15) >> 4;
   // the first tile's coordinates are fetched before the weights are staged (both global latencies overlap)
@@ -3343,7 +3363,7 @@ __device__ __forceinline__ void fused_multi_closure_body(const FusedMultiArgs& a
   // bound by the latency of its parameter loads -- 2.97 us for two images one after the other at C1, measured)
   const real* prm = prm_k;
 #if !NDQ_F64
-  if constexpr (pull_supported<C>()) {
+  if constexpr (pull_supported<C>() && !ST::ON) {      // (no pull mode for evaluation sites: the prologue counts networks)
     if (pull.enabled) {
       // finish the previous epoch for all K networks (every thread of the workgroup on every network), results in LDS
       float* pn0 = lds + K * WS;
@@ -3382,14 +3402,20 @@ __device__ __forceinline__ void fused_multi_closure_body(const FusedMultiArgs& a
 #pragma unroll
       for (int d = 0; d < C::D; ++d) xn[d] = coords[(size_t)d * a.ldc + nn1];
     }
+    real xs[C::D];                                       // what this wave's network is evaluated at: x, or x with boundary values
+#pragma unroll
+    for (int d = 0; d < C::D; ++d) {
+      xs[d] = x[d];
+      if constexpr (ST::ON) xs[d] = ((ST::vmask(k) >> d) & 1u) ? ST::value(k, d) : xs[d];
+    }
     LayerState<C> st[C::L];
     real4 h[C::NS][C::NB];
     KeptPlanes<C> kp;
-    tile_forward<C, TRAIN>(ldsw, lane, q, x, st, h, kp, stage);
+    tile_forward<C, TRAIN>(ldsw, lane, q, xs, st, h, kp, stage);
     real* xr = xchg + (par * G + g) * (K * C::NS * 16);        // [K][NS][16 points] of this tile
     {
       real mine[C::NS];
-      tile_output<C, TRAIN>(ldsw, q, x, h, mine);
+      tile_output<C, TRAIN>(ldsw, q, xs, h, mine);
       if (q == 0) {
 #pragma unroll
         for (int s = 0; s < C::NS; ++s) xr[(k * C::NS + s) * 16 + p] = mine[s];
@@ -3431,7 +3457,7 @@ __device__ __forceinline__ void fused_multi_closure_body(const FusedMultiArgs& a
         for (int kk = 1; kk < K; ++kk) v = (k == kk) ? gout[kk][s] : v;
         go[s] = valid ? v : 0.f;
       }
-      tile_backward<C>(ldsw, stage, lane, p, q, x, go, st, acc, kp);
+      tile_backward<C>(ldsw, stage, lane, p, q, xs, go, st, acc, kp);
     }
   }
 #ifdef NDQ_PHASE_TS
@@ -3442,8 +3468,25 @@ __device__ __forceinline__ void fused_multi_closure_body(const FusedMultiArgs& a
     // the G waves of a network add up among themselves (all networks at once: same barrier sequence), regions in that
     // network's own staging area; block_reduce_store addresses its regions behind "the" weight image of its base
     real* base = work + k * multi_group_floats<C, K>() - C::ldsWeightsEnd(true);
-    block_reduce_store<C, G, multi_regions<C, K>()>(base, acc, g, lane, p, q, part_k + (size_t)blk * C::P, prm_k,
-                                                     g * 64 + lane, G * 64);
+    if constexpr (!ST::ON) {
+      block_reduce_store<C, G, multi_regions<C, K>()>(base, acc, g, lane, p, q, part_k + (size_t)blk * C::P, prm_k,
+                                                       g * 64 + lane, G * 64);
+    } else {
+      // evaluation sites: every site's sum into LDS (its weight image: the tile loop is over for every wave once the first
+      // barrier of block_reduce_store has been passed), then the sites of a network in index order -> the workgroup's row
+      static_assert(WS >= C::P, "a site's gradient row fits its weight image");
+      block_reduce_store<C, G, multi_regions<C, K>()>(base, acc, g, lane, p, q, lds + k * WS, prm_k, g * 64 + lane, G * 64);
+      __syncthreads();
+      if (ST::rank(k) == 0) {
+        for (int i = g * 64 + lane; i < C::P; i += G * 64) {
+          real v = lds[k * WS + i];
+#pragma unroll
+          for (int kk = 1; kk < K; ++kk)
+            if (kk > k && ST::net(kk) == net_k) v += lds[kk * WS + i];
+          part_k[(size_t)blk * C::P + i] = v;
+        }
+      }
+    }
   }
   lsum = point_sum(quad_sum(lsum));                      // non-zero in the waves of network 0 only
   __syncthreads();
@@ -3459,21 +3502,21 @@ __device__ __forceinline__ void fused_multi_closure_body(const FusedMultiArgs& a
   NDQ_TS(3);
 }
 
-template <class C, int K, class PW, bool TRAIN>
+template <class C, int K, class PW, bool TRAIN, class ST = SiteIdentity>
 __global__ __launch_bounds__(multi_threads<K>()) void fused_multi_closure_kernel(FusedMultiArgs a) {
   extern __shared__ __attribute__((aligned(16))) real lds[];
   const PullArgs none{};
-  fused_multi_closure_body<C, K, PW, TRAIN>(a, lds, blockIdx.x, gridDim.x, none, false, MultiLoopView{});
+  fused_multi_closure_body<C, K, PW, TRAIN, ST>(a, lds, blockIdx.x, gridDim.x, none, false, MultiLoopView{});
 }
 
 // training + validation batch in one launch, as fused_closure_tv_kernel
-template <class C, int K, class PW>
+template <class C, int K, class PW, class ST = SiteIdentity>
 __global__ __launch_bounds__(multi_threads<K>()) void fused_multi_closure_tv_kernel(FusedMultiArgs t, FusedMultiArgs v, int train_blocks,
                                                                                     PullArgs pull) {
   extern __shared__ __attribute__((aligned(16))) real lds[];
   const bool writer = blockIdx.x == 0;
-  if ((int)blockIdx.x < train_blocks) fused_multi_closure_body<C, K, PW, true>(t, lds, blockIdx.x, train_blocks, pull, writer, MultiLoopView{});
-  else fused_multi_closure_body<C, K, PW, false>(v, lds, (int)blockIdx.x - train_blocks, (int)gridDim.x - train_blocks, pull, writer, MultiLoopView{});
+  if ((int)blockIdx.x < train_blocks) fused_multi_closure_body<C, K, PW, true, ST>(t, lds, blockIdx.x, train_blocks, pull, writer, MultiLoopView{});
+  else fused_multi_closure_body<C, K, PW, false, ST>(v, lds, (int)blockIdx.x - train_blocks, (int)gridDim.x - train_blocks, pull, writer, MultiLoopView{});
 }
 
 template <class C, int K> constexpr size_t fused_multi_lds_bytes(bool train);

@@ -172,6 +172,10 @@ def trace_system(nets, conditions, diff_eqs, n_coords, compute_func_val=None, lo
             callables compute."""
             n_captured = len(g.captured)
             twins_before = set(getattr(g, "twins", ()))
+            # boundary columns of Neumann ends (symbolic.Graph.vcoord) are replayed, not created again: fresh ones would be
+            # other coordinates, other sites and other nodes, and every probe would report a changed system
+            n_vcoords, n_sites, known_sites = len(g.vcoords), len(g.site_net), dict(g._sites)
+            g._vreplay = 0
             g.ext_log = []
             eq_probe.last_ext = None
             try:
@@ -200,6 +204,14 @@ def trace_system(nets, conditions, diff_eqs, n_coords, compute_func_val=None, lo
                                   "columns, once per re-trace: they should be free of side effects.)", RuntimeWarning)
                 return False
             finally:
+                g._vreplay = None
+                for idx in [i for i in g.vcoords if i >= n_coords + n_vcoords]:     # (what a CHANGED boundary left behind)
+                    del g.vcoords[idx]
+                del g.site_net[n_sites:]
+                for key in [k for k in g._sites if k not in known_sites]:
+                    g.net_deps.pop(g._sites[key], None)
+                    g.net_nout.pop(g._sites[key], None)
+                    del g._sites[key]
                 del g.captured[n_captured:]       # (the probe's own captures are the same tensors again)
                 for key in [k for k in getattr(g, "twins", ()) if k not in twins_before]:
                     del g.twins[key]              # (twins of the tensors this probe created: they would pile up)
@@ -317,12 +329,21 @@ def trace_system(nets, conditions, diff_eqs, n_coords, compute_func_val=None, lo
         multi-network closure kernel (one launch for the whole system) can serve them; a network then carries at most
         a few streams it does not need -- these systems are launch-bound, not compute-bound."""
         K = len(nets)
-        if not (2 <= K <= 4) or len(streams) != K or len(g.site_net) != K or os.environ.get("NDQ_NO_MULTI_FUSE"):
+        S = len(g.site_net)
+        if S > K:
+            # ... and the same for 2..4 evaluation sites of fewer networks (Neumann ends: codegen.fuse_mode "sites"): every
+            # site reads all batch coordinates, some replaced by a boundary value -- stream sets are per input POSITION
+            if not (2 <= S <= 4) or len(streams) != S or f64 or os.environ.get("NDQ_NO_SITE_FUSE"):
+                return
+            if any(len(st.deps) != n_coords or any(c != a and c not in g.vcoords for a, c in enumerate(st.deps))
+                   for st in streams.values()):
+                return
+        elif not (2 <= K <= 4) or len(streams) != K or os.environ.get("NDQ_NO_MULTI_FUSE"):
             return
         shape = {(i["d"], i["hidden"], i["layers"], i["act"], i["n_out"], i["skip"], i["actp"], i["widths"], i["mono"]) for i in infos}
         if len(shape) != 1 or infos[0]["n_out"] != 1 or codegen.padded_width(infos[0]["hidden"]) > 48:
             return
-        if any(tuple(st.deps) != tuple(range(n_coords)) for st in streams.values()):
+        if S == K and any(tuple(st.deps) != tuple(range(n_coords)) for st in streams.values()):
             return
         sts = list(streams.values())
         if any(st.mask3 or getattr(st, "mask4", 0) for st in sts):
@@ -524,7 +545,7 @@ class FusedSystem:
         """Does csrc/ndq_mlp.h give this shape an 8-wave build at all?  (Cfg::BWD_THREADS: per-wave state of more than 40
         fragment blocks keeps the whole register file, i.e. 4 waves -- no point compiling to find that out)"""
         mode = codegen.fuse_mode(self.program, self.descs)
-        if mode == "multi":
+        if mode in ("multi", "sites"):
             return False            # K x G waves, one per SIMD, whatever the batch size (csrc/ndq_mlp.h: multi_threads)
         if mode == "wide_multi":
             return False            # one wave per SIMD holds K networks' accumulators (csrc/ndq_wide.h: NDQ_WIDE_THREADS)

@@ -107,7 +107,16 @@ class Graph:
         self._sites = {}         # (network index, deps) -> site
 
     def vcoord(self, value):
-        """A new virtual coordinate: a column that holds ``value`` at every point (node id)."""
+        """A new virtual coordinate: a column that holds ``value`` at every point (node id).  While a re-trace replays the
+        compiled one (``_vreplay``: engine.trace_system's eq_probe) the k-th request gets the k-th coordinate of that trace
+        again if it asks for the same value -- an unchanged system must arrive at the same nodes."""
+        k = getattr(self, "_vreplay", None)
+        if k is not None:
+            idx = self.n_coords + k
+            if self.vcoords.get(idx) == float(value):
+                self._vreplay = k + 1
+                return self.coord(idx)
+            self._vreplay = None                 # another boundary than the compiled one: fresh coordinates from here on
         idx = self.n_coords + len(self.vcoords)
         self.vcoords[idx] = float(value)
         return self.coord(idx)
