@@ -946,11 +946,13 @@ class FusedKernel:
         return self.lib.ndq_fused_blocks(n)
 
 
-def _cache_key(source):
+def _cache_key(source, more_flags=()):
     """Cache key of a generated module: its source (with the package location factored out, so a relocated checkout
-    keeps its cache), the kernel headers it instantiates and the extra compile flags."""
+    keeps its cache), the kernel headers it instantiates and the extra compile flags (NDQ_JIT_FLAGS, then ``more_flags``:
+    the same key whichever of the two ways a flag came in)."""
     text = source.replace(HERE, "<neurodiffeq_amd>")
-    return hashlib.sha1((text + _header_digest() + " ".join(_extra_flags()) + _build_tag()).encode()).hexdigest()[:16]
+    flags = _extra_flags() + list(more_flags)
+    return hashlib.sha1((text + _header_digest() + " ".join(flags) + _build_tag()).encode()).hexdigest()[:16]
 
 
 def _build_tag():
@@ -1317,14 +1319,15 @@ def can_fuse_f64(program, descs):
     return program.n_nets == 1 and can_fuse(program, descs) and fuse_mode(program, descs) == "tile" and descs[0].hidden <= 64
 
 
-def build_fused(program: PointwiseProgram, desc, force=False, threads=None, f64=False):
+def build_fused(program: PointwiseProgram, desc, force=False, threads=None, f64=False, more_flags=()):
     """Compile the fused closure kernel of a single-network system for gfx950 (in-tree cache keyed by the generated
     source AND the kernel header it instantiates).  ``threads=512``: the 8-wave build (two waves per SIMD where the
-    per-wave state fits 256 registers; csrc/ndq_mlp.h NDQ_BWD_THREADS) the engine uses for large batches."""
+    per-wave state fits 256 registers; csrc/ndq_mlp.h NDQ_BWD_THREADS) the engine uses for large batches.
+    ``more_flags``: compile flags behind those of NDQ_JIT_FLAGS, as if they had been given there (the same cache entry)."""
     os.makedirs(JIT_DIR, exist_ok=True)
     source = program.fused_source(desc, f64=f64)
-    flags = _extra_flags() + ([f"-DNDQ_BWD_THREADS={int(threads)}"] if threads else []) + (WIDE_FLAGS if is_wide(desc) else [])
-    key = _cache_key(source + (f"|threads={int(threads)}" if threads else ""))
+    flags = _extra_flags() + list(more_flags) + ([f"-DNDQ_BWD_THREADS={int(threads)}"] if threads else []) + (WIDE_FLAGS if is_wide(desc) else [])
+    key = _cache_key(source + (f"|threads={int(threads)}" if threads else ""), more_flags)
     so = os.path.join(JIT_DIR, f"fused_{key}.so")
     src = os.path.join(JIT_DIR, f"fused_{key}.hip")
     if os.path.exists(so) and not force:

@@ -438,6 +438,11 @@ constexpr bool act_has_s4(int act) {
                           // pass's products and planes cut down (round 6) it is: 17.52 -> 17.03 us on one box, 16.23 -> 16.09 on
                           // another (profiles/r06h_flags_ab_c2.txt, r06j_own_tile_ab.txt) -- on.  0: the ds_bpermute route.
 #endif
+#ifndef NDQ_EPILOGUE_RS
+#define NDQ_EPILOGUE_RS 1 // single-launch closure kernels of H = 32 single-output networks: reduction epilogue with a butterfly
+                          // reduce-scatter, dense deposits and swizzled matrix deposits (block_reduce_store_rs); the same
+                          // summation trees, so the same bits.  0: block_reduce_store and the separate loss sum, as before
+#endif
 #ifndef NDQ_SPLIT_PAIRS
 #define NDQ_SPLIT_PAIRS 0   // split3 on 2-wide vectors: 3.5 % fewer VALU instructions in C3's closure kernel, no time gained
                             // (C3 418.4 -> 419.8 us, C2 8-wave 19.9 -> 19.7 us on MI355X): off
@@ -2904,6 +2909,158 @@ __device__ __forceinline__ void block_reduce_store(real* lds, GradAcc<C>& acc, i
   }
 }
 
+// ------------------------------------------------------------------------------------------------ reduce-scatter epilogue
+// The same reduction for the single-launch closure kernels of H = 32 single-output networks (NDQ_EPILOGUE_RS), with
+// three costs taken out.  Layout of the regions, final pass, out[] and every summation tree are block_reduce_store's.
+//  * point_sum() leaves all 16 lanes of a row with the same total.  Its row_ror 8, 4, 2, 1 pair lane i with i ^ 8, then
+//    -- the sums having period 8, 4, 2 -- with i ^ 4, i ^ 2, i ^ 1: the xor butterfly.  reduce_scatter() runs the same
+//    pairings in the same order on 16 values at once and after each level keeps the half of them the lane's bit selects:
+//    lane p ends up with the total of value p, added up in point_sum()'s tree.  15 adds per 16 values instead of 64.
+//  * the per-unit totals then sit one per lane and are deposited by full-width stores, not unit by unit under p == 0.
+//  * rs_swizzle(): the matrix deposits of the four lane groups q fall on one set of 16 banks (row stride 32 floats); inside
+//    the layer's 32 x 32 block, row bit 0 is flipped for q >= 2 and the column half for odd q, an involution of [0, 1024)
+//    that the final pass reads through.  Either 32-lane half of a store then covers 32 banks, the wave all 64.
+//  * the wave's loss sum travels in the spare slot of its region behind the same barrier.
+template <int CTRL>
+__device__ __forceinline__ float dpp_pair(float v) {    // v + the CTRL partner's v (a lane without a partner: v)
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+// One butterfly level on 2 h values: a lane whose bit `up` is clear goes on with the pair sums of x[0 .. h), the others
+// with those of x[h .. 2 h).  LO / HI: DPP controls under which the lanes of either kind read their xor partner (what the
+// other kind of lane computes with it is dropped) -- two fused DPP adds and a select per value kept, no copies.
+template <int LO, int HI, int H2>
+__device__ __forceinline__ void rs_level(float* x, bool up) {
+#pragma unroll
+  for (int m = 0; m < H2; ++m) {
+    const float lo = dpp_pair<LO>(x[m]), hi = dpp_pair<HI>(x[H2 + m]);
+    x[m] = up ? hi : lo;
+  }
+}
+// N = 16: total of x[p] over the row's lanes, in lane p.  N = 8: total of x[p & 7] (distance 8 is then a plain sum).
+template <int N>
+__device__ __forceinline__ float reduce_scatter(float (&x)[N], int p) {
+  static_assert(N == 16 || N == 8, "one or half a value per lane of a DPP row");
+  if constexpr (N == 16) {
+    rs_level<0x128, 0x128, 8>(x, (p & 8) != 0);       // distance 8: row_ror:8
+  } else {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) x[m] = dpp_pair<0x128>(x[m]);
+  }
+  rs_level<0x104, 0x114, 4>(x, (p & 4) != 0);         // distance 4: row_shl:4 reads lane i + 4, row_shr:4 lane i - 4
+  rs_level<0x4e, 0x4e, 2>(x, (p & 2) != 0);           // distance 2: quad_perm:[2,3,0,1]
+  rs_level<0xb1, 0xb1, 1>(x, (p & 1) != 0);           // distance 1: quad_perm:[1,0,3,2]
+  return x[0];
+}
+
+// entry e = 32 j + k of a 32 x 32 block -> where it is kept: j ^= bit 3 of j, k ^= 16 * (bit 2 of j)
+__host__ __device__ constexpr int rs_swizzle(int e) { return e ^ (((e >> 8) & 1) << 5) ^ (((e >> 7) & 1) << 4); }
+
+// the per-unit accumulators as NIN + L + 1 "octets" of 8 values [b][r] (unit j = 16 b + 4 q + r): W1 column by column,
+// b1, b_2 .. b_L, Wout; octet O's unit j lives at rs_octet_off + j * rs_octet_stride of the flat vector
+template <class C, int O> __device__ __forceinline__ auto& rs_octet(GradAcc<C>& acc) {
+  if constexpr (O < C::NIN) return acc.w1[O];
+  else if constexpr (O == C::NIN) return acc.b1;
+  else if constexpr (O < C::NIN + C::L) return acc.b[O - C::NIN - 1];
+  else return acc.wout;
+}
+template <class C> constexpr int rs_octet_off(int o) {
+  return o < C::NIN ? C::offW1 + o : o == C::NIN ? C::offb1 : o < C::NIN + C::L ? C::offb(o - C::NIN + 1) : C::offWout;
+}
+template <class C> constexpr int rs_octet_stride(int o) { return o < C::NIN ? C::NIN : 1; }
+
+template <class C, int WAVES>
+constexpr bool epilogue_rs() {             // one deposit round (a region per wave), a spare slot behind the P sums
+  return NDQ_EPILOGUE_RS != 0 && NDQ_F64 == 0 && C::NOUT == 1 && C::NB == 2 && !C::RAGGED && !C::ACC_LDS && !C::WG32 &&
+         C::ACTP == 0 && bwd_regions<C>(WAVES) == WAVES && ((C::P + 3) & ~3) > C::P;
+}
+
+// loss_out: the workgroup's loss partial, the waves' lsum (per-lane partial sums) added up in wave order
+template <class C, int WAVES>
+__device__ __forceinline__ void block_reduce_store_rs(real* lds, GradAcc<C>& acc, int wave, int lane, int p, int q,
+                                                      real* __restrict__ out, real lsum, real* __restrict__ loss_out) {
+  constexpr int PP = (C::P + 3) & ~3;
+  constexpr int NO = C::NIN + C::L + 1, NG = (NO + 1) / 2;
+  static_assert(C::H == 32 && C::hr(1) == 32 && C::offW(2) % 32 == 0, "32 x 32 blocks on 32-float boundaries");
+  const int tid = threadIdx.x, nt = blockDim.x;
+  real* red0 = lds + C::ldsWeightsEnd(true);
+  const real bsum = point_sum(quad_sum(acc.bout));
+  real ssum[C::D];
+#pragma unroll
+  for (int a = 0; a < C::D; ++a) ssum[a] = (C::SKIP != 0) ? point_sum(quad_sum(acc.skip[a])) : 0.f;
+  lsum = point_sum(quad_sum(lsum));
+  float tot[NG];                           // lane p: octet 2 g + (p >> 3), unit 16 b + 4 q + r with (b, r) = ((p >> 2) & 1, p & 3)
+  sfor<NG>([&](auto g_) {
+    constexpr int g = decltype(g_)::value;
+    if constexpr (2 * g + 1 < NO) {
+      float x[16];
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        x[m] = rs_octet<C, 2 * g>(acc)[m >> 2][m & 3];
+        x[8 + m] = rs_octet<C, 2 * g + 1>(acc)[m >> 2][m & 3];
+      }
+      tot[g] = reduce_scatter<16>(x, p);
+    } else {
+      float x[8];
+#pragma unroll
+      for (int m = 0; m < 8; ++m) x[m] = rs_octet<C, 2 * g>(acc)[m >> 2][m & 3];
+      tot[g] = reduce_scatter<8>(x, p);
+    }
+  });
+  __syncthreads();  // every wave is done with its staging tile
+  real* red = red0 + wave * PP;
+  const int unit = 16 * ((p >> 2) & 1) + 4 * q + (p & 3);
+  sfor<NG>([&](auto g_) {
+    constexpr int g = decltype(g_)::value;
+    if constexpr (2 * g + 1 < NO) {
+      const int off = p < 8 ? rs_octet_off<C>(2 * g) : rs_octet_off<C>(2 * g + 1);
+      const int stride = p < 8 ? rs_octet_stride<C>(2 * g) : rs_octet_stride<C>(2 * g + 1);
+      red[off + unit * stride] = tot[g];
+    } else {
+      if (p < 8) red[rs_octet_off<C>(2 * g) + unit * rs_octet_stride<C>(2 * g)] = tot[g];
+    }
+  });
+  // matrix entry (j, k) = (16 jb + 4 q + r, 16 kb + p) at rs_swizzle: row bit 0 (of r) flipped by q >> 1, kb by q & 1
+  int at[2][2];
+#pragma unroll
+  for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) at[rb][kb] = (4 * q + (rb ^ (q >> 1))) * 32 + 16 * (kb ^ (q & 1)) + p;
+#pragma unroll
+  for (int l = 0; l < C::L - 1; ++l)
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[C::offW(l + 2) + 512 * jb + 32 * (r & 2) + at[r & 1][kb]] = acc.w[l][jb][kb][r];
+  if (lane == 0) {
+    red[C::offbout] = bsum;
+    if constexpr (C::SKIP != 0) {
+#pragma unroll
+      for (int a = 0; a < C::D; ++a) red[C::offS + a] = ssum[a];
+    }
+    red[C::P] = lsum;
+  }
+  __syncthreads();
+  for (int i = tid; i < C::P; i += nt) {
+    int at_i = i;
+    if constexpr (C::L > 1) {
+      const int e = i - C::offW(2), l = e / (32 * 33);        // hidden layer l + 2: 32 x 32 weights, then 32 biases
+      const int el = e - l * (32 * 33);
+      if (e >= 0 && l < C::L - 1 && el < 1024) at_i = i - el + rs_swizzle(el);
+    }
+    real v = red0[at_i];
+#pragma unroll
+    for (int r = 1; r < WAVES; ++r) v += red0[r * PP + at_i];
+    out[i] = v;
+  }
+  if (tid == 0) {
+    real v = 0.f;
+    for (int w = 0; w < WAVES; ++w) v += red0[w * PP + C::P];
+    loss_out[0] = v;
+  }
+}
+
 template <class C>
 __global__ __launch_bounds__(C::BWD_THREADS) void mlp_jet_bwd_kernel(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) real lds[];
@@ -3145,17 +3302,21 @@ __device__ __forceinline__ void fused_closure_body(const FusedArgs& a, real* lds
   __syncthreads();
   NDQ_TS(2);
 #endif
-  if constexpr (TRAIN) block_reduce_store<C, WAVES>(lds, acc, wave, lane, p, q, a.partials + (size_t)blk * C::P, a.params);
-  // loss: lanes (only q == 0 lanes are non-zero) -> wave -> workgroup, fixed order
-  lsum = point_sum(quad_sum(lsum));
-  __syncthreads();
   real* wl = lds + C::ldsWeightsEnd(TRAIN);
-  if (lane == 0) wl[wave] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    real v = 0.f;
-    for (int w = 0; w < WAVES; ++w) v += wl[w];
-    a.loss_partials[blk] = v;
+  if constexpr (TRAIN && epilogue_rs<C, WAVES>()) {      // gradient and loss sums behind one pair of barriers
+    block_reduce_store_rs<C, WAVES>(lds, acc, wave, lane, p, q, a.partials + (size_t)blk * C::P, lsum, a.loss_partials + blk);
+  } else {
+    if constexpr (TRAIN) block_reduce_store<C, WAVES>(lds, acc, wave, lane, p, q, a.partials + (size_t)blk * C::P, a.params);
+    // loss: lanes (only q == 0 lanes are non-zero) -> wave -> workgroup, fixed order
+    lsum = point_sum(quad_sum(lsum));
+    __syncthreads();
+    if (lane == 0) wl[wave] = lsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      real v = 0.f;
+      for (int w = 0; w < WAVES; ++w) v += wl[w];
+      a.loss_partials[blk] = v;
+    }
   }
   if constexpr (TRAIN) theta_block_sum<PW::NT>(tsum, wl + 16, WAVES, a.theta_partials ? a.theta_partials + (size_t)blk * PW::NT : nullptr);
   NDQ_TS(3);
