@@ -517,6 +517,8 @@ struct SITES {{
             return self._group_source(desc, wide=True, nets=K)
         if mode == "sites":
             return self._site_source(desc)
+        if mode == "wide_sites":
+            return self._group_source(desc, wide=True, sites=self.n_sites)
         ns = self.streams[0].n_streams
         nsym = max(len(self.symbols), 1)
         jet = (lambda k, loc: f"jets[{loc}]") if K == 1 else (lambda k, loc: f"jets[{k}][{loc}]")
@@ -642,17 +644,21 @@ using CFG = {mlp_cfg(desc, 1)};
 }};
 {host}"""
 
-    def _group_source(self, desc, wide=False, nets=1):
+    def _group_source(self, desc, wide=False, nets=1, sites=0):
         """Source of the grouped single-launch closure kernel (csrc/ndq_mlp.h: fused_group_closure_kernel): one network
         with any number of outputs, reading any subset of the batch coordinates; the per-point function runs on one
         point per lane, stream values and adjoint seeds are exchanged through an LDS tile.
         ``wide``: the closure kernel of csrc/ndq_wide.h (one hidden layer of 65 .. 512 units) -- the same per-point
         interface, stream rows [n_streams][n_out] without padding.
         ``nets`` = K > 1 (with ``wide``): wide_multi_closure_kernel, K networks of ONE WideCfg behind one launch -- the same
-        per-point interface with the K rows side by side, [net][n_streams][n_out]."""
+        per-point interface with the K rows side by side, [net][n_streams][n_out].
+        ``sites`` = S > 1 (with ``wide``): the same kernel behind the traits of ``_site_traits`` -- S evaluation sites of fewer
+        networks (Neumann ends), rows [site][n_streams][n_out], unit images and gradient rows per network."""
         st = self.streams[0]
         width = st.n_streams * st.n_out
-        assert nets == 1 or (wide and all(self.streams[k].n_streams * self.streams[k].n_out == width for k in range(nets)))
+        assert not sites or (wide and nets == 1)
+        rows = sites or nets
+        assert rows == 1 or (wide and all(self.streams[k].n_streams * self.streams[k].n_out == width for k in range(rows)))
         gw = 1 if st.n_out == 1 else (st.n_out + 15) // 16 * 16      # row layout [n_streams][gw] (ndq::group_w)
         if wide:
             gw = st.n_out
@@ -665,8 +671,8 @@ using CFG = {mlp_cfg(desc, 1)};
             used[(k, loc)] = idx
             loads.append(f"    s[{idx}] = srow[{row(k, loc)}];")
         stores = [f"    grow[{row(k, loc)}] = {'g[%d]' % used[(k, loc)] if (k, loc) in used else '0.0f'};"
-                  for k in range(nets) for loc in range(width)]
-        deps = list(st.deps)
+                  for k in range(rows) for loc in range(width)]
+        deps = list(range(self.n_coords)) if sites else list(st.deps)   # (a site's boundary values: the traits, not dep)
         dep_fn = " : ".join(f"d == {d} ? {c}" for d, c in enumerate(deps)) + " : 0"
         header = "ndq_mlp.h"                 # found through -I csrc (_hipcc.BASE_FLAGS): sources and cache keys do not depend on the checkout path
         neq, nf = len(self.residuals), len(self.funcs)
@@ -684,9 +690,19 @@ using CFG = {mlp_cfg(desc, 1)};
             kern = lambda train: f"ndq::wide_multi_closure_kernel<CFG, {nets}, PW, {train}>"
             lds = lambda train: f"(ndq::wide_multi_closure_lds_bytes<CFG, {nets}, PW>())"
             kern_tv = f"ndq::wide_multi_closure_tv_kernel<CFG, {nets}, PW>"
-        host = _closure_host(nets, "CFG::BWD_THREADS", points, "CFG::BWD_THREADS / 64", kern, kern_tv, lds)
+        traits, what = "", (f" with {nets} networks" if nets > 1 else "")
+        if sites:
+            # S slices, N unit images (csrc/ndq_wide.h: wide_multi_closure_body with site traits); parameter sets and
+            # gradient partials per network behind the multi-network argument struct, as the narrow site modules
+            N = self.n_nets
+            kern = lambda train: f"ndq::wide_multi_closure_kernel<CFG, {sites}, PW, {train}, SITES>"
+            lds = lambda train: f"(ndq::wide_multi_closure_lds_bytes<CFG, {sites}, PW, {N}>())"
+            kern_tv = f"ndq::wide_multi_closure_tv_kernel<CFG, {sites}, PW, SITES>"
+            traits, what = self._site_traits(), f" with {N} network(s) at {sites} evaluation sites"
+        host = _closure_host(self.n_nets if sites else nets, "CFG::BWD_THREADS", points, "CFG::BWD_THREADS / 64", kern, kern_tv, lds,
+                             sites=bool(sites))
         return f"""// GENERATED by neurodiffeq_amd/codegen.py -- grouped single-launch closure kernel (forward streams -> LDS exchange ->
-// per-point stage, one point per lane -> reverse pass) of one PDE system{f" with {nets} networks" if nets > 1 else ""}, gfx950.
+// per-point stage, one point per lane -> reverse pass) of one PDE system{what}, gfx950.
 {CLOSURE_PRODUCTS}#include "{header}"
 #define NDQ_PW_INLINE __device__ __forceinline__
 #ifndef NDQ_MAX_BLOCKS
@@ -696,7 +712,7 @@ using CFG = {mlp_cfg(desc, 1)};
 namespace {{
 using CFG = {cfg_t};
 static_assert(CFG::NS * CFG::NOUT == {width}, "stream layout of the traced program and of the kernel disagree");
-struct PW {{
+{traits}struct PW {{
   // NC rows of the coordinate block per point: the batch coordinates, then ND data columns; NT trainable scalars
   static constexpr int NEQ = {neq}, NF = {nf}, ND = {self.n_data}, NT = {self.n_theta}, NC = {self.n_coords} + ND, NR = {self.n_r};
   static constexpr int dep(int d) {{ return {dep_fn}; }}     // batch coordinate fed to network input d
@@ -1355,9 +1371,15 @@ def fuse_mode(program: PointwiseProgram, descs=None):
              shape and stream set, one output, H <= 48, fp32, no third- / fourth-order streams; every site reads all batch
              coordinates, some of them replaced by a boundary value (fused_multi_closure_kernel with site traits, one wave
              group per site); NDQ_NO_SITE_FUSE is its off-switch.
+    "wide_sites"  the same family on networks with ONE hidden layer of 65 .. 512 units: 2..4 sites of fewer networks of one
+             shape and stream set, one output, fp32, no skip / trainable activation parameters / monomial front end, no
+             third- / fourth-order streams (wide_multi_closure_kernel with site traits: one wave runs all sites of a tile
+             and sums a network's gradient over its sites in its own registers); NDQ_NO_WIDE_SITE_FUSE is its off-switch.
     None     three-kernel pipeline."""
     K = program.n_nets
     if K >= 1 and program.n_sites > K:
+        if descs is not None and 0 in descs and is_wide(descs[0]):
+            return "wide_sites" if _sites_ok(program, descs, wide=True) else None
         return "sites" if _sites_ok(program, descs) else None
     if K < 1 or K > 4 or program.n_sites != K or any(k not in program.streams for k in range(K)):
         return None
@@ -1391,15 +1413,21 @@ def fuse_mode(program: PointwiseProgram, descs=None):
     return "multi"
 
 
-def _sites_ok(program, descs):
-    """``fuse_mode``: may the evaluation-site closure kernel serve this system?"""
+def _sites_ok(program, descs, wide=False):
+    """``fuse_mode``: may the evaluation-site closure kernel serve this system?  (``wide``: the one of csrc/ndq_wide.h)"""
     S, nc = program.n_sites, program.n_coords
-    if not (2 <= S <= 4) or os.environ.get("NDQ_NO_SITE_FUSE") or any(k not in program.streams for k in range(S)):
+    off = "NDQ_NO_WIDE_SITE_FUSE" if wide else "NDQ_NO_SITE_FUSE"
+    if not (2 <= S <= 4) or os.environ.get(off) or any(k not in program.streams for k in range(S)):
         return False
     if descs is None or any(k not in descs for k in range(S)) or len({descs[k].key() for k in range(S)}) != 1:
         return False
     d0 = descs[0]
-    if is_wide(d0) or padded_width(d0.hidden) > 48 or d0.n_out != 1 or d0.mask3 or getattr(d0, "mask4", 0):
+    if wide:
+        if not is_wide(d0) or d0.hidden > 512 or d0.layers != 1 or d0.skip or d0.actp or d0.mono:
+            return False
+    elif is_wide(d0) or padded_width(d0.hidden) > 48:
+        return False
+    if d0.n_out != 1 or d0.mask3 or getattr(d0, "mask4", 0):
         return False
     for k in range(S):               # (fp64 systems never get here with a say: can_fuse_f64 takes "tile" only)
         st = program.streams[k]

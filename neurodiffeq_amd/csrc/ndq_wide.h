@@ -688,7 +688,7 @@ __global__ __launch_bounds__(C::THREADS) void wide_closure_tv_kernel(FusedArgs t
 // slice k (counted from the top) while its reduction rows overlay only reduction rows and slices no earlier network wrote.
 template <class C, int K>
 struct WideMulti {
-  static_assert(K >= 2 && K <= kMaxFusedNets, "2 .. 4 networks of one shape");
+  static_assert(K >= 2 && K <= kMaxFusedNets, "2 .. 4 networks of one shape, or 2 .. 4 evaluation sites of fewer");
   static constexpr int NXP = C::NX > 0 ? C::NX : 1;
   static constexpr int FIELDS = C::U * (C::D + 1 + NXP + C::NOUT + (C::NOUT == 1 ? C::NS : 0));   // floats of a lane's WideUnits
   static constexpr int IMG = FIELDS * C::UL;                                                   // ... of a network's image
@@ -742,15 +742,31 @@ __device__ __forceinline__ void wide_units_from_image(const real* img, int ul, W
   }
 }
 
+// number of parameter sets behind K evaluation sites (the identity: K)
+template <class ST, int K> constexpr int wide_site_nets() {
+  int n = 0;
+  for (int k = 0; k < K; ++k) n = ST::net(k) + 1 > n ? ST::net(k) + 1 : n;
+  return n;
+}
+
 // PW (generated, codegen.py): the per-point interface of wide_closure_body with the K networks' rows side by side --
 // srow / grow [net][stream][out], K * C::NC values, the order fused_multi_closure_kernel hands its jets[K][NS].
-template <class C, int K, class PW, bool TRAIN>
+// ST: evaluation sites (csrc/ndq_mlp.h: SiteIdentity is the contract and the default -- K networks, one site each).  With
+// sites on, K counts SITES: pass k of a tile runs network ST::net(k) on the tile's coordinates with the entries in
+// ST::vmask(k) replaced by the literals ST::value(k, d); stream rows, seed rows and kept states are per site (K slices),
+// unit images, gradient accumulators and partial rows per NETWORK (N = wide_site_nets < K).  A network's gradient is the sum
+// over its sites taken in the wave's own accumulator registers, site after site in index order, and its output-bias seed is
+// added up per POINT before it joins the running sum (u - u(x_b): the sites' seeds are exact negatives there, and the sum
+// is an exact zero instead of the rounding noise a row-wise sum of per-site partials would leave).
+template <class C, int K, class PW, bool TRAIN, class ST = SiteIdentity>
 __device__ __forceinline__ void wide_multi_closure_body(const FusedMultiArgs& a, real* lds, const int blk, const int nblk) {
   using M = WideMulti<C, K>;
-  static_assert(C::WAVES >= K, "wave k stages network k's image");
+  constexpr int N = wide_site_nets<ST, K>();
+  static_assert(N >= 1 && N <= K && (ST::ON || N == K), "K sites of N networks");
+  static_assert(C::WAVES >= N, "wave k stages network k's image");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = lane & 15, q = lane >> 4;
   const int ul = lane & (C::UL - 1), pl = lane / C::UL;
-  real* work = lds + K * M::IMG;               // behind the images: the waves' tile regions, later the reduction rows
+  real* work = lds + N * M::IMG;               // behind the images: the waves' tile regions, later the reduction rows
   real* wl = work + wave * M::waveFloats;
   // coordinates one tile ahead, as wide_closure_body (the first tile's load overlaps the staging of the images)
   const int ntiles = (a.n + 15) >> 4;
@@ -761,7 +777,7 @@ __device__ __forceinline__ void wide_multi_closure_body(const FusedMultiArgs& a,
 #pragma unroll
     for (int d = 0; d < PW::NC; ++d) ccn[d] = a.coords[(size_t)d * a.ldc + nn0];
   }
-  sfor<K>([&](auto k_) {
+  sfor<N>([&](auto k_) {
     constexpr int k = decltype(k_)::value;
     if (wave == k) {
       WideUnits<C> un;
@@ -770,10 +786,10 @@ __device__ __forceinline__ void wide_multi_closure_body(const FusedMultiArgs& a,
     }
   });
   __syncthreads();
-  WideGrad<C> g[K];
-  real gbo[K][C::NOUT];
+  WideGrad<C> g[N];
+  real gbo[N][C::NOUT];
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
+  for (int k = 0; k < N; ++k) {
     if constexpr (TRAIN) wide_grad_zero<C>(g[k]);
 #pragma unroll
     for (int o = 0; o < C::NOUT; ++o) gbo[k][o] = 0.f;
@@ -799,13 +815,24 @@ __device__ __forceinline__ void wide_multi_closure_body(const FusedMultiArgs& a,
       constexpr int d = decltype(d_)::value;
       xv[d] = cc[PW::dep(d)];
     });
+    // inputs of pass k: the tile's coordinates, boundary values where site k has them
+    auto site_inputs = [&](auto k_, real (&xs)[C::D]) {
+      constexpr int k = decltype(k_)::value;
+      sfor<C::D>([&](auto d_) {
+        constexpr int d = decltype(d_)::value;
+        if constexpr (ST::ON && ((ST::vmask(k) >> d) & 1u) != 0) xs[d] = ST::value(k, d);
+        else xs[d] = xv[d];
+      });
+    };
     WideKept<C> kept[M::KEEP_ALL ? K : 1];
-    // ---- K forward passes: network k's stream rows -> slice k
+    // ---- K forward passes: pass k's stream rows -> slice k
     sfor<K>([&](auto k_) {
       constexpr int k = decltype(k_)::value;
       WideUnits<C> un;
-      wide_units_from_image<C>(lds + k * M::IMG, ul, un);
-      wide_tile_forward<C, TRAIN && M::KEEP_ALL, true>(un, xv, wl + M::fwd_base(k), a.params[k] + C::offbout, lane, ul, pl,
+      wide_units_from_image<C>(lds + ST::net(k) * M::IMG, ul, un);
+      real xs[C::D];
+      site_inputs(k_, xs);
+      wide_tile_forward<C, TRAIN && M::KEEP_ALL, true>(un, xs, wl + M::fwd_base(k), a.params[ST::net(k)] + C::offbout, lane, ul, pl,
                                                       kept[M::KEEP_ALL ? k : 0]);
     });
     // ---- per-point stage, once, on lanes 0 .. 15; seeds -> the K seed slices
@@ -835,10 +862,30 @@ __device__ __forceinline__ void wide_multi_closure_body(const FusedMultiArgs& a,
         if constexpr (TRAIN) {
 #pragma unroll
           for (int j = 0; j < PW::NT; ++j) tsum[j] += gth[j];
+          if constexpr (!ST::ON) {
 #pragma unroll
-          for (int k = 0; k < K; ++k)
+            for (int k = 0; k < K; ++k)
 #pragma unroll
-            for (int o = 0; o < C::NOUT; ++o) gbo[k][o] += grow[k * C::NC + o];
+              for (int o = 0; o < C::NOUT; ++o) gbo[k][o] += grow[k * C::NC + o];
+          } else {
+            // the point's value-stream seeds of a network's sites, added up first (index order), then into the running sum
+            sfor<N>([&](auto m_) {
+              constexpr int m = decltype(m_)::value;
+#pragma unroll
+              for (int o = 0; o < C::NOUT; ++o) {
+                real t = 0.f;
+                bool first = true;
+                sfor<K>([&](auto k_) {
+                  constexpr int k = decltype(k_)::value;
+                  if constexpr (ST::net(k) == m) {
+                    t = first ? grow[k * C::NC + o] : t + grow[k * C::NC + o];
+                    first = false;
+                  }
+                });
+                gbo[m][o] += t;
+              }
+            });
+          }
         }
         if (a.resid) {
 #pragma unroll
@@ -850,15 +897,17 @@ __device__ __forceinline__ void wide_multi_closure_body(const FusedMultiArgs& a,
         }
       }
     }
-    // ---- K reverse passes
+    // ---- K reverse passes: pass k into the accumulators of its network
     if constexpr (TRAIN) {
       wave_lds_sync();
       sfor<K>([&](auto k_) {
         constexpr int k = decltype(k_)::value;
         WideUnits<C> un;
-        wide_units_from_image<C>(lds + k * M::IMG, ul, un);
-        if constexpr (!M::KEEP_ALL) wide_tile_forward<C, true, false>(un, xv, wl, nullptr, lane, ul, pl, kept[0]);
-        wide_tile_backward<C>(un, xv, wl + M::bwd_base(k), pl, kept[M::KEEP_ALL ? k : 0], g[k]);
+        wide_units_from_image<C>(lds + ST::net(k) * M::IMG, ul, un);
+        real xs[C::D];
+        site_inputs(k_, xs);
+        if constexpr (!M::KEEP_ALL) wide_tile_forward<C, true, false>(un, xs, wl, nullptr, lane, ul, pl, kept[0]);
+        wide_tile_backward<C>(un, xs, wl + M::bwd_base(k), pl, kept[M::KEEP_ALL ? k : 0], g[ST::net(k)]);
       });
     }
     wave_lds_sync();
@@ -866,7 +915,7 @@ __device__ __forceinline__ void wide_multi_closure_body(const FusedMultiArgs& a,
   // per-network block partial rows, network by network through the same reduction rows (fixed order; the call begins with a
   // workgroup barrier, so the previous network's rows have been read by then)
   if constexpr (TRAIN) {
-    sfor<K>([&](auto k_) {
+    sfor<N>([&](auto k_) {
       constexpr int k = decltype(k_)::value;
       WideUnits<C> un;
       wide_units_from_image<C>(lds + k * M::IMG, ul, un);
@@ -886,25 +935,26 @@ __device__ __forceinline__ void wide_multi_closure_body(const FusedMultiArgs& a,
   if constexpr (TRAIN) theta_block_sum<PW::NT>(tsum, ws + 16, C::WAVES, a.theta_partials ? a.theta_partials + (size_t)blk * PW::NT : nullptr);
 }
 
-template <class C, int K, class PW> constexpr size_t wide_multi_closure_lds_bytes() {
+// N: unit images in LDS -- the networks; K with the identity traits, fewer than K for K evaluation sites
+template <class C, int K, class PW, int N = K> constexpr size_t wide_multi_closure_lds_bytes() {
   using M = WideMulti<C, K>;
   const int tiles = C::WAVES * M::waveFloats;
   const int red = M::redFloats + 32 + C::WAVES * (PW::NT > 0 ? PW::NT : 1);
-  return sizeof(real) * (K * M::IMG + (tiles > red ? tiles : red));
+  return sizeof(real) * (N * M::IMG + (tiles > red ? tiles : red));
 }
 
-template <class C, int K, class PW, bool TRAIN>
+template <class C, int K, class PW, bool TRAIN, class ST = SiteIdentity>
 __global__ __launch_bounds__(C::THREADS) void wide_multi_closure_kernel(FusedMultiArgs a) {
   extern __shared__ __attribute__((aligned(16))) real lds[];
-  wide_multi_closure_body<C, K, PW, TRAIN>(a, lds, blockIdx.x, gridDim.x);
+  wide_multi_closure_body<C, K, PW, TRAIN, ST>(a, lds, blockIdx.x, gridDim.x);
 }
 
 // training batch and validation batch in one launch, as wide_closure_tv_kernel
-template <class C, int K, class PW>
+template <class C, int K, class PW, class ST = SiteIdentity>
 __global__ __launch_bounds__(C::THREADS) void wide_multi_closure_tv_kernel(FusedMultiArgs t, FusedMultiArgs v, int train_blocks, PullArgs) {
   extern __shared__ __attribute__((aligned(16))) real lds[];
-  if ((int)blockIdx.x < train_blocks) wide_multi_closure_body<C, K, PW, true>(t, lds, blockIdx.x, train_blocks);
-  else wide_multi_closure_body<C, K, PW, false>(v, lds, (int)blockIdx.x - train_blocks, (int)gridDim.x - train_blocks);
+  if ((int)blockIdx.x < train_blocks) wide_multi_closure_body<C, K, PW, true, ST>(t, lds, blockIdx.x, train_blocks);
+  else wide_multi_closure_body<C, K, PW, false, ST>(v, lds, (int)blockIdx.x - train_blocks, (int)gridDim.x - train_blocks);
 }
 
 }  // namespace ndq

@@ -330,10 +330,15 @@ def trace_system(nets, conditions, diff_eqs, n_coords, compute_func_val=None, lo
         a few streams it does not need -- these systems are launch-bound, not compute-bound."""
         K = len(nets)
         S = len(g.site_net)
+        i0 = infos[0]
+        # sites of networks with one hidden layer of 65 .. 512 units: codegen.fuse_mode "wide_sites", a switch of its own
+        wide_sites = (S > K and i0["layers"] == 1 and 64 < i0["hidden"] <= 512
+                      and not (i0["skip"] or i0["actp"] or i0["mono"] or i0["widths"]))
         if S > K:
             # ... and the same for 2..4 evaluation sites of fewer networks (Neumann ends: codegen.fuse_mode "sites"): every
             # site reads all batch coordinates, some replaced by a boundary value -- stream sets are per input POSITION
-            if not (2 <= S <= 4) or len(streams) != S or f64 or os.environ.get("NDQ_NO_SITE_FUSE"):
+            off = "NDQ_NO_WIDE_SITE_FUSE" if wide_sites else "NDQ_NO_SITE_FUSE"
+            if not (2 <= S <= 4) or len(streams) != S or f64 or os.environ.get(off):
                 return
             if any(len(st.deps) != n_coords or any(c != a and c not in g.vcoords for a, c in enumerate(st.deps))
                    for st in streams.values()):
@@ -341,7 +346,7 @@ def trace_system(nets, conditions, diff_eqs, n_coords, compute_func_val=None, lo
         elif not (2 <= K <= 4) or len(streams) != K or os.environ.get("NDQ_NO_MULTI_FUSE"):
             return
         shape = {(i["d"], i["hidden"], i["layers"], i["act"], i["n_out"], i["skip"], i["actp"], i["widths"], i["mono"]) for i in infos}
-        if len(shape) != 1 or infos[0]["n_out"] != 1 or codegen.padded_width(infos[0]["hidden"]) > 48:
+        if len(shape) != 1 or infos[0]["n_out"] != 1 or (codegen.padded_width(infos[0]["hidden"]) > 48 and not wide_sites):
             return
         if S == K and any(tuple(st.deps) != tuple(range(n_coords)) for st in streams.values()):
             return
@@ -547,7 +552,7 @@ class FusedSystem:
         mode = codegen.fuse_mode(self.program, self.descs)
         if mode in ("multi", "sites"):
             return False            # K x G waves, one per SIMD, whatever the batch size (csrc/ndq_mlp.h: multi_threads)
-        if mode == "wide_multi":
+        if mode in ("wide_multi", "wide_sites"):
             return False            # one wave per SIMD holds K networks' accumulators (csrc/ndq_wide.h: NDQ_WIDE_THREADS)
         if mode == "group":
             return os.environ.get("NDQ_GROUP_WIDE", "0") == "1"     # experiment: 8 waves with 32-point groups
