@@ -480,7 +480,8 @@ NDQ_PW_INLINE float ndq_pw_loss(const float* r) {{ return {term}; }}
         fused_multi_closure_kernel for 2..4 networks of one shape and stream set) specialised with this program's
         per-point function.  desc: the ndq_mlp_desc shared by all networks.
         f64: the same module in double (csrc/ndq_mlp.h under NDQ_F64: per-point GEMMs on the f64 MFMA, no bf16 planes, no
-        pull / loop mode) -- one network, plain closure only (``can_fuse_f64``)."""
+        pull / loop mode) -- one network on the plain closure (``can_fuse_f64``), or 2..4 networks on the multi-network
+        closure (``can_fuse_multi_f64``)."""
         if f64:
             return "#define NDQ_F64 1\n" + source_f64(self._fused_source(desc, True))
         return self._fused_source(desc, False)
@@ -510,7 +511,7 @@ struct SITES {{
     def _fused_source(self, desc, f64):
         K = self.n_nets
         mode = fuse_mode(self, {k: desc for k in range(max(K, self.n_sites))})
-        assert mode is not None and not (f64 and (mode != "tile" or K != 1))
+        assert mode is not None and not (f64 and not ((mode == "tile" and K == 1) or mode == "multi"))
         if mode in ("group", "wide"):
             return self._group_source(desc, wide=(mode == "wide"))
         if mode == "wide_multi":
@@ -1333,6 +1334,21 @@ def can_fuse_f64(program, descs):
     """fp64 systems: the single-launch closure exists for ONE network on the plain closure kernel (no grouped / wide /
     multi-network variant in double)."""
     return program.n_nets == 1 and can_fuse(program, descs) and fuse_mode(program, descs) == "tile" and descs[0].hidden <= 64
+
+
+def can_fuse_multi_f64(program, descs):
+    """fp64 systems of 2..4 networks: the multi-network closure kernel compiled in double (``fuse_mode`` "multi": one shape
+    and stream set, one output each, every network reading all coordinates, padded width <= 48) -- no evaluation sites, no
+    third- / fourth-order streams, no skip weights / trainable activation parameters / monomial front end.  Whether the
+    module fits the LDS of one workgroup is the engine's question to the built module (``ndq_fused_lds_bytes``).
+    ``can_fuse_f64`` keeps its meaning: the one-network closure."""
+    K = program.n_nets
+    if not (2 <= K <= 4) or program.n_sites != K or descs is None or fuse_mode(program, descs) != "multi":
+        return False
+    d0 = descs[0]
+    if d0.n_out != 1 or d0.mask3 or getattr(d0, "mask4", 0) or d0.skip or d0.actp or d0.mono:
+        return False
+    return not any(program.streams[k].mask3 or getattr(program.streams[k], "mask4", 0) for k in range(K))
 
 
 def build_fused(program: PointwiseProgram, desc, force=False, threads=None, f64=False, more_flags=()):

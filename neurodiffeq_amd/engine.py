@@ -378,6 +378,18 @@ def trace_system(nets, conditions, diff_eqs, n_coords, compute_func_val=None, lo
     return program, descs
 
 
+def wants_closure(program, descs, f64):
+    """Does a single-launch closure kernel exist for this traced system?  fp32: any mode of ``codegen.fuse_mode``.  fp64: one
+    network on the plain closure kernel (``codegen.can_fuse_f64``) or 2..4 narrow networks on the multi-network one
+    (``codegen.can_fuse_multi_f64``, which NDQ_NO_MULTI_FUSE turns off with the fp32 mode); NDQ_F64_CLOSURE=0 keeps every fp64
+    system on the three-kernel pipeline."""
+    if not f64:
+        return codegen.can_fuse(program, descs)
+    if os.environ.get("NDQ_F64_CLOSURE", "1") == "0":
+        return False
+    return codegen.can_fuse_f64(program, descs) or codegen.can_fuse_multi_f64(program, descs)
+
+
 class FusedSystem:
     def __init__(self, nets, conditions, diff_eqs, n_coords, device, compute_func_val=None, single_kernel=True,
                  loss="l2", metrics=(), dtype=torch.float32, volatile=frozenset()):
@@ -389,7 +401,8 @@ class FusedSystem:
             raise _lib.NdqError("the fused path needs an MI355X (device 'cuda'); no CPU fallback exists for it")
         # dtype float64 (the reference's default precision, neurodiffeq/__init__.py:22): the fp64 build of the stream kernels
         # (libndq64.so) with the generated pointwise kernel compiled in double; single-network systems on the plain closure
-        # kernel get that kernel compiled in double as well (codegen.can_fuse_f64); the epoch tail runs on the device
+        # kernel get that kernel compiled in double as well (codegen.can_fuse_f64), systems of 2..4 narrow networks the
+        # multi-network closure kernel (codegen.can_fuse_multi_f64); the epoch tail runs on the device
         # (ndq64_epoch_tail); pull / loop mode, the multi-epoch fit() call and the 8-wave build are fp32 only
         from . import _canary
         _canary.check()              # once per process: the gfx950 hazard reproducer through / without the assembly fix-up pass
@@ -423,9 +436,9 @@ class FusedSystem:
         # first use of a system: its pointwise kernel and its single-launch closure kernel are compiled CONCURRENTLY (two
         # hipcc pipelines side by side; cached in-tree afterwards)
         from . import _hipcc
-        # (fp64: one network on the plain closure kernel compiled in double; NDQ_F64_CLOSURE=0: three-kernel pipeline only)
-        want_fused = single_kernel and (codegen.can_fuse_f64(self.program, self.descs) and os.environ.get("NDQ_F64_CLOSURE", "1") != "0"
-                                        if self.f64 else codegen.can_fuse(self.program, self.descs))
+        # (fp64: one network on the plain closure kernel compiled in double, or 2..4 networks on the multi-network one --
+        # codegen.can_fuse_multi_f64; NDQ_F64_CLOSURE=0: three-kernel pipeline only)
+        want_fused = single_kernel and wants_closure(self.program, self.descs, self.f64)
         with _hipcc.deferred():
             pw_so = codegen.build(self.program, f64=self.f64)
             fused_so = codegen.build_fused(self.program, self.descs[0], f64=self.f64) if want_fused else None
@@ -966,7 +979,7 @@ class FusedSystem:
         training workgroups == the training launch (which has just run: ``b`` still holds its partial sums), loss
         partial sums of its validation workgroups == the forward-only launch; alone and together."""
         fk = b["fusedk"]
-        dev, f32 = self.device, torch.float32
+        dev, f32 = self.device, self.dt          # (the module's scalar type: double for an fp64 system)
         seed = 1.0 / (float(n_global) * self.loss_norm)
         params_pp = (_c_vp * len(self.flat))(*[fp.flat.data_ptr() for fp in self.flat])
         want_parts = [t.clone() for t in b["fused_partials_all"]]
@@ -1050,7 +1063,8 @@ class FusedSystem:
     def launches_per_step(self):
         """Kernel launches of one native training epoch with one batch (bench.py reports it per config)."""
         if self.fusedk is not None and self.f64:
-            return 4                                     # closure kernel, gradient sum, loss sum, epoch tail (in double)
+            # closure kernel, loss sum; per network: gradient sum, epoch tail (in double) -- 4 for one network, 6 for two
+            return 2 + 2 * len(self.flat)
         if self.fusedk is not None:
             return 2                                     # closure kernel + ONE sums/tail kernel (all networks)
         # pipeline: forward per site, pointwise, (adjoint + sums) per site, loss sum, epoch tail per network
