@@ -13,6 +13,7 @@ import ctypes
 import hashlib
 import os
 import re
+from collections import namedtuple
 
 from .symbolic import Graph, TraceUnsupported
 
@@ -196,22 +197,24 @@ def _forward_lines(g, order, val, symbols=()):
     return L
 
 
-def _closure_host(K, threads, points, slots, kern, kern_tv, lds, kern_loop=None, lds_loop=None, sites=False):
+def _closure_host(mode, N, R, f64):
     """Tail of a generated closure module: the traits struct ``Closure`` (what differs between the closure kernels; the
     contract is the file comment of csrc/ndq_closure_host.h), then that header -- the launchers and every ndq_fused_* export.
-    kern(train) / lds(train): C++ text of the plain kernel and of its LDS bytes; kern_loop=None: no loop-mode kernel.
-    sites: an evaluation-site module -- K parameter sets behind the multi-network argument struct (K = 1 included), no pull mode."""
-    no_pull = "\n  static constexpr bool NO_PULL = true;" if sites else ""
+    mode: the ``ClosureMode`` record, whose C++ texts are filled with N parameter sets and R stream rows (networks or
+    evaluation sites).  The loop-mode kernel is fp32 only (csrc/ndq_tail.h) and exists for up to ``mode.loop_max`` rows."""
+    text = lambda t, **kw: t.format(N=N, R=R, **kw)
+    loop = bool(mode.loop) and not f64 and R <= mode.loop_max
+    no_pull = "\n  static constexpr bool NO_PULL = true;" if mode.traits else ""
     return f"""struct Closure {{
   using Cfg = CFG;
   using Pw = PW;
-  using Args = ndq::{'FusedArgs' if K == 1 and not sites else 'FusedMultiArgs'};
-  static constexpr int K = {K}, THREADS = {threads}, POINTS = {points}, SLOTS = {slots};{no_pull}
-  static constexpr auto train = &{kern('true')};
-  static constexpr auto eval = &{kern('false')};
-  static constexpr auto tv = &{kern_tv};
-  static constexpr auto loop = {'&' + kern_loop if kern_loop else 'nullptr'};
-  static constexpr size_t LDS_TRAIN = {lds('true')}, LDS_EVAL = {lds('false')}, LDS_LOOP = {lds_loop or 0};
+  using Args = ndq::{mode.args};
+  static constexpr int K = {N}, THREADS = {text(mode.threads)}, POINTS = {mode.points}, SLOTS = {text(mode.slots)};{no_pull}
+  static constexpr auto train = &{text(mode.kern, train='true')};
+  static constexpr auto eval = &{text(mode.kern, train='false')};
+  static constexpr auto tv = &{text(mode.tv)};
+  static constexpr auto loop = {'&' + text(mode.loop) if loop else 'nullptr'};
+  static constexpr size_t LDS_TRAIN = {text(mode.lds, train='true')}, LDS_EVAL = {text(mode.lds, train='false')}, LDS_LOOP = {text(mode.lds_loop) if loop else 0};
 }};
 }}  // namespace
 #include "ndq_closure_host.h"
@@ -508,212 +511,59 @@ struct SITES {{
 }};
 """
 
+    def closure_mode(self, desc):
+        """The ``ClosureMode`` record of the closure kernel that serves this program when every site has descriptor ``desc``."""
+        name = fuse_mode(self, {k: desc for k in range(max(self.n_nets, self.n_sites))})
+        assert name is not None
+        return MODES[name]
+
     def _fused_source(self, desc, f64):
-        K = self.n_nets
-        mode = fuse_mode(self, {k: desc for k in range(max(K, self.n_sites))})
-        assert mode is not None and not (f64 and not ((mode == "tile" and K == 1) or mode == "multi"))
-        if mode in ("group", "wide"):
-            return self._group_source(desc, wide=(mode == "wide"))
-        if mode == "wide_multi":
-            return self._group_source(desc, wide=True, nets=K)
-        if mode == "sites":
-            return self._site_source(desc)
-        if mode == "wide_sites":
-            return self._group_source(desc, wide=True, sites=self.n_sites)
-        ns = self.streams[0].n_streams
-        nsym = max(len(self.symbols), 1)
-        jet = (lambda k, loc: f"jets[{loc}]") if K == 1 else (lambda k, loc: f"jets[{k}][{loc}]")
-        gj = (lambda k, loc: f"gj[{loc}]") if K == 1 else (lambda k, loc: f"gj[{k}][{loc}]")
-        loads, stores = [], []
-        used = {}
-        for idx, i in enumerate(self.symbols):
-            k, loc = self.sym_location(i)
-            used[(k, loc)] = idx
-            loads.append(f"    s[{idx}] = {jet(k, loc)};")
-        for k in range(K):
-            for loc in range(ns):
-                stores.append(f"    {gj(k, loc)} = {'g[%d]' % used[(k, loc)] if (k, loc) in used else '0.0f'};")
-        header = "ndq_mlp.h"                 # found through -I csrc (_hipcc.BASE_FLAGS): sources and cache keys do not depend on the checkout path
-        neq, nf = len(self.residuals), len(self.funcs)
-        jets_t = "const float (&jets)[CFG::NS]" if K == 1 else f"const float (&jets)[{K}][CFG::NS]"
-        gj_t = "float (&gj)[CFG::NS]" if K == 1 else f"float (&gj)[{K}][CFG::NS]"
-        kern = (lambda train: f"ndq::fused_closure_kernel<CFG, PW, {train}>") if K == 1 else \
-            (lambda train: f"ndq::fused_multi_closure_kernel<CFG, {K}, PW, {train}>")
-        lds = (lambda train: f"ndq::fused_lds_bytes<CFG>({train})") if K == 1 else \
-            (lambda train: f"(ndq::fused_multi_lds_bytes<CFG, {K}>({train}))")
-        # workgroup shape: waves x tiles per round (multi-network closure: K x G waves, G tile slots -- csrc/ndq_mlp.h)
-        threads = "CFG::BWD_THREADS" if K == 1 else f"ndq::multi_threads<{K}>()"
-        tiles_per_block = "CFG::BWD_THREADS / 64" if K == 1 else f"ndq::multi_group<{K}>()"
-        kern_tv = "ndq::fused_closure_tv_kernel<CFG, PW>" if K == 1 else f"ndq::fused_multi_closure_tv_kernel<CFG, {K}, PW>"
-        if f64:
-            kern_loop = lds_loop = None          # (loop / pull mode: fp32 only, csrc/ndq_tail.h)
-        elif K == 1:
-            kern_loop, lds_loop = "ndq::fused_closure_loop_kernel<CFG, PW>", "ndq::fused_loop_lds_bytes<CFG>()"
-        elif K == 2:
-            kern_loop, lds_loop = f"ndq::fused_multi_closure_loop_kernel<CFG, {K}, PW>", f"(ndq::fused_multi_loop_lds_bytes<CFG, {K}>())"
-        else:
-            kern_loop = lds_loop = None
-        host = _closure_host(K, threads, 16, tiles_per_block, kern, kern_tv, lds, kern_loop, lds_loop)
-        # hidden-layer weight gradients from the bf16x3 planes through transposing LDS reads (csrc/ndq_mlp.h Cfg::WG_TR;
-        # shapes it does not cover, or whose K images would not fit the LDS, ignore the switch)
-        wg_tr = f"#ifndef NDQ_WG_TR\n#define NDQ_WG_TR 1\n#endif\n#define NDQ_WG_TR_K {K}\n" + CLOSURE_PRODUCTS
-        return f"""// GENERATED by neurodiffeq_amd/codegen.py -- single-launch closure kernel (forward streams + pointwise stage +
-// reverse pass) of one PDE system with {K} network(s), gfx950.
-{wg_tr}#include "{header}"
-#define NDQ_PW_INLINE __device__ __forceinline__
-#ifndef NDQ_MAX_BLOCKS
-#define NDQ_MAX_BLOCKS 256     // closure workgroups per launch (one per CU; experiments: 512 = two 8-wave workgroups per CU)
-#endif
-{self.point_fn_source()}
-namespace {{
-using CFG = {mlp_cfg(desc, 1)};
-struct PW {{
-  // ND per-point data columns (rows D .. D + ND of the coordinate block), NT trainable scalars of the equations
-  static constexpr int NEQ = {neq}, NF = {nf}, NR = {self.n_r}, ND = {self.n_data}, NT = {self.n_theta};
-  static __device__ __forceinline__ float loss(const float* r) {{ return ndq_pw_loss(r); }}
-  // xe: the point's ND data values, then the NT scalars;  gth (want_adj): per-point adjoints of the scalars
-  static __device__ __forceinline__ void apply(const float (&x)[CFG::D], const float* xe, {jets_t}, float seed,
-                                               int want_adj, float (&r)[{self.n_r}], float (&f)[{max(nf, 1)}],
-                                               {gj_t}, float* gth) {{
-    float c[CFG::D + ND + NT], s[{nsym}], g[{nsym} + NT];
-#pragma unroll
-    for (int d = 0; d < CFG::D; ++d) c[d] = x[d];
-#pragma unroll
-    for (int j = 0; j < ND + NT; ++j) c[CFG::D + j] = xe[j];
-{chr(10).join(loads)}
-    ndq_pw_point(c, s, seed, want_adj, r, f, g);
-{chr(10).join(stores)}
-#pragma unroll
-    for (int j = 0; j < NT; ++j) gth[j] = g[{len(self.symbols)} + j];
-  }}
-}};
-{host}"""
-
-    def _site_source(self, desc):
-        """The multi-network closure kernel for a system with evaluation sites (Neumann ends): S = 2..4 sites of fewer
-        networks on S wave groups.  Stream arrays are per site, parameter sets and gradient partials per network."""
-        S, ns = self.n_sites, self.streams[0].n_streams
-        nsym = max(len(self.symbols), 1)
-        loads, stores, used = [], [], {}
-        for idx, i in enumerate(self.symbols):
-            k, loc = self.sym_location(i)
-            used[(k, loc)] = idx
-            loads.append(f"    s[{idx}] = jets[{k}][{loc}];")
-        for k in range(S):
-            for loc in range(ns):
-                stores.append(f"    gj[{k}][{loc}] = {'g[%d]' % used[(k, loc)] if (k, loc) in used else '0.0f'};")
-        neq, nf = len(self.residuals), len(self.funcs)
-        kern = lambda train: f"ndq::fused_multi_closure_kernel<CFG, {S}, PW, {train}, SITES>"
-        lds = lambda train: f"(ndq::fused_multi_lds_bytes<CFG, {S}>({train}))"
-        host = _closure_host(self.n_nets, f"ndq::multi_threads<{S}>()", 16, f"ndq::multi_group<{S}>()", kern,
-                             f"ndq::fused_multi_closure_tv_kernel<CFG, {S}, PW, SITES>", lds, sites=True)
-        # (NDQ_WG_TR_K: weight images in LDS -- one per site, a network with two sites is staged twice.)  No CLOSURE_PRODUCTS:
-        # every GEMM keeps all six bf16 plane products.  A network's gradient is the SUM of its sites' and those nearly cancel
-        # (u - u(x_b) - w u_x(x_b): the output bias drops out exactly), so the 4- / 3-product reverse and weight-gradient
-        # GEMMs of the other closure modules, 1e-6 of each site's gradient, come to 1e-5 of the network's (measured: heat
-        # equation with two Neumann ends 1.25e-5 against fp64 with them, 2e-7 without); these systems are launch-bound
-        wg_tr = f"#ifndef NDQ_WG_TR\n#define NDQ_WG_TR 1\n#endif\n#define NDQ_WG_TR_K {S}\n"
-        return f"""// GENERATED by neurodiffeq_amd/codegen.py -- single-launch closure kernel (forward streams + pointwise stage +
-// reverse pass) of one PDE system with {self.n_nets} network(s) at {S} evaluation sites, gfx950.
-{wg_tr}#include "ndq_mlp.h"
-#define NDQ_PW_INLINE __device__ __forceinline__
-#ifndef NDQ_MAX_BLOCKS
-#define NDQ_MAX_BLOCKS 256     // closure workgroups per launch (one per CU)
-#endif
-{self.point_fn_source()}
-namespace {{
-using CFG = {mlp_cfg(desc, 1)};
-{self._site_traits()}struct PW {{
-  // ND per-point data columns (rows D .. D + ND of the coordinate block), NT trainable scalars of the equations
-  static constexpr int NEQ = {neq}, NF = {nf}, NR = {self.n_r}, ND = {self.n_data}, NT = {self.n_theta};
-  static __device__ __forceinline__ float loss(const float* r) {{ return ndq_pw_loss(r); }}
-  // x: the batch point (every site's real inputs);  jets / gj: streams and their adjoints, per SITE
-  static __device__ __forceinline__ void apply(const float (&x)[CFG::D], const float* xe, const float (&jets)[{S}][CFG::NS],
-                                               float seed, int want_adj, float (&r)[{self.n_r}], float (&f)[{max(nf, 1)}],
-                                               float (&gj)[{S}][CFG::NS], float* gth) {{
-    float c[CFG::D + ND + NT], s[{nsym}], g[{nsym} + NT];
-#pragma unroll
-    for (int d = 0; d < CFG::D; ++d) c[d] = x[d];
-#pragma unroll
-    for (int j = 0; j < ND + NT; ++j) c[CFG::D + j] = xe[j];
-{chr(10).join(loads)}
-    ndq_pw_point(c, s, seed, want_adj, r, f, g);
-{chr(10).join(stores)}
-#pragma unroll
-    for (int j = 0; j < NT; ++j) gth[j] = g[{len(self.symbols)} + j];
-  }}
-}};
-{host}"""
-
-    def _group_source(self, desc, wide=False, nets=1, sites=0):
-        """Source of the grouped single-launch closure kernel (csrc/ndq_mlp.h: fused_group_closure_kernel): one network
-        with any number of outputs, reading any subset of the batch coordinates; the per-point function runs on one
-        point per lane, stream values and adjoint seeds are exchanged through an LDS tile.
-        ``wide``: the closure kernel of csrc/ndq_wide.h (one hidden layer of 65 .. 512 units) -- the same per-point
-        interface, stream rows [n_streams][n_out] without padding.
-        ``nets`` = K > 1 (with ``wide``): wide_multi_closure_kernel, K networks of ONE WideCfg behind one launch -- the same
-        per-point interface with the K rows side by side, [net][n_streams][n_out].
-        ``sites`` = S > 1 (with ``wide``): the same kernel behind the traits of ``_site_traits`` -- S evaluation sites of fewer
-        networks (Neumann ends), rows [site][n_streams][n_out], unit images and gradient rows per network."""
-        st = self.streams[0]
+        """One generated closure module, assembled from the mode's record: title comment, defines, kernel header, the per-point
+        function, CFG, the site traits where the mode has them, PW around one of the two per-point interfaces, and the host
+        tail.  N parameter sets, R stream rows (one per network, or one per evaluation site).
+        jets: the kernels of csrc/ndq_mlp.h hand ``apply`` a point's streams as arrays ``jets[R][NS]`` / ``gj`` (one output per
+              network, every network reads all coordinates).
+        rows: one point per lane; stream values and adjoint seeds travel through an LDS tile as rows ``srow`` / ``grow``,
+              [row][n_streams][n_out] -- any number of outputs, any subset of the batch coordinates as inputs (``PW::dep``; a
+              site's boundary values are the traits' business, not dep's).  The grouped kernel of csrc/ndq_mlp.h pads the outputs
+              of a stream to 16 (ndq::group_w), the kernels of csrc/ndq_wide.h do not."""
+        mode = self.closure_mode(desc)
+        assert mode.f64 or not f64
+        N, R, st = self.n_nets, self.n_sites, self.streams[0]
         width = st.n_streams * st.n_out
-        assert not sites or (wide and nets == 1)
-        rows = sites or nets
-        assert rows == 1 or (wide and all(self.streams[k].n_streams * self.streams[k].n_out == width for k in range(rows)))
-        gw = 1 if st.n_out == 1 else (st.n_out + 15) // 16 * 16      # row layout [n_streams][gw] (ndq::group_w)
-        if wide:
-            gw = st.n_out
-        row = lambda k, loc: k * width + (loc // st.n_out) * gw + loc % st.n_out
-        nsym = max(len(self.symbols), 1)
-        used = {}
-        loads = []
+        if mode.rows:
+            assert all(self.streams[k].n_streams * self.streams[k].n_out == width for k in range(R))
+            gw = st.n_out if not mode.padded_rows or st.n_out == 1 else (st.n_out + 15) // 16 * 16
+            at = lambda k, loc: f"[{k * width + (loc // st.n_out) * gw + loc % st.n_out}]"
+            src, dst = "srow", "grow"
+        else:
+            at = (lambda k, loc: f"[{loc}]") if R == 1 else (lambda k, loc: f"[{k}][{loc}]")
+            src, dst = "jets", "gj"
+        used, loads = {}, []
         for idx, i in enumerate(self.symbols):
             k, loc = self.sym_location(i)
             used[(k, loc)] = idx
-            loads.append(f"    s[{idx}] = srow[{row(k, loc)}];")
-        stores = [f"    grow[{row(k, loc)}] = {'g[%d]' % used[(k, loc)] if (k, loc) in used else '0.0f'};"
-                  for k in range(rows) for loc in range(width)]
-        deps = list(range(self.n_coords)) if sites else list(st.deps)   # (a site's boundary values: the traits, not dep)
-        dep_fn = " : ".join(f"d == {d} ? {c}" for d, c in enumerate(deps)) + " : 0"
-        header = "ndq_mlp.h"                 # found through -I csrc (_hipcc.BASE_FLAGS): sources and cache keys do not depend on the checkout path
+            loads.append(f"    s[{idx}] = {src}{at(k, loc)};")
+        stores = [f"    {dst}{at(k, loc)} = {'g[%d]' % used[(k, loc)] if (k, loc) in used else '0.0f'};"
+                  for k in range(R) for loc in range(width)]
+        nsym = max(len(self.symbols), 1)
         neq, nf = len(self.residuals), len(self.funcs)
-        kern = lambda train: f"ndq::fused_group_closure_kernel<CFG, PW, {train}>"
-        lds = lambda train: f"ndq::group_lds_bytes<CFG>({train})"
-        kern_tv = "ndq::fused_group_closure_tv_kernel<CFG, PW>"
-        cfg_t, points = mlp_cfg(desc, desc.n_out), "16 * ndq::group_tiles<CFG>()"
-        if wide:
-            header = "ndq_wide.h"
-            kern = lambda train: f"ndq::wide_closure_kernel<CFG, PW, {train}>"
-            lds = lambda train: "(ndq::wide_closure_lds_bytes<CFG, PW>())"
-            kern_tv = "ndq::wide_closure_tv_kernel<CFG, PW>"
-            cfg_t, points = wide_cfg(desc), 16
-        if nets > 1:
-            kern = lambda train: f"ndq::wide_multi_closure_kernel<CFG, {nets}, PW, {train}>"
-            lds = lambda train: f"(ndq::wide_multi_closure_lds_bytes<CFG, {nets}, PW>())"
-            kern_tv = f"ndq::wide_multi_closure_tv_kernel<CFG, {nets}, PW>"
-        traits, what = "", (f" with {nets} networks" if nets > 1 else "")
-        if sites:
-            # S slices, N unit images (csrc/ndq_wide.h: wide_multi_closure_body with site traits); parameter sets and
-            # gradient partials per network behind the multi-network argument struct, as the narrow site modules
-            N = self.n_nets
-            kern = lambda train: f"ndq::wide_multi_closure_kernel<CFG, {sites}, PW, {train}, SITES>"
-            lds = lambda train: f"(ndq::wide_multi_closure_lds_bytes<CFG, {sites}, PW, {N}>())"
-            kern_tv = f"ndq::wide_multi_closure_tv_kernel<CFG, {sites}, PW, SITES>"
-            traits, what = self._site_traits(), f" with {N} network(s) at {sites} evaluation sites"
-        host = _closure_host(self.n_nets if sites else nets, "CFG::BWD_THREADS", points, "CFG::BWD_THREADS / 64", kern, kern_tv, lds,
-                             sites=bool(sites))
-        return f"""// GENERATED by neurodiffeq_amd/codegen.py -- grouped single-launch closure kernel (forward streams -> LDS exchange ->
-// per-point stage, one point per lane -> reverse pass) of one PDE system{what}, gfx950.
-{CLOSURE_PRODUCTS}#include "{header}"
-#define NDQ_PW_INLINE __device__ __forceinline__
-#ifndef NDQ_MAX_BLOCKS
-#define NDQ_MAX_BLOCKS 256     // closure workgroups per launch (one per CU; experiments: 512 = two 8-wave workgroups per CU)
-#endif
-{self.point_fn_source()}
-namespace {{
-using CFG = {cfg_t};
-static_assert(CFG::NS * CFG::NOUT == {width}, "stream layout of the traced program and of the kernel disagree");
-{traits}struct PW {{
+        guard = "    if (!want_adj) return;\n" if mode.rows else ""
+        point = f"""{chr(10).join(loads)}
+    ndq_pw_point(c, s, seed, want_adj, r, f, g);
+{guard}{chr(10).join(stores)}
+#pragma unroll
+    for (int j = 0; j < NT; ++j) gth[j] = g[{len(self.symbols)} + j];
+  }}
+}};
+"""
+        if mode.rows:
+            deps = list(range(self.n_coords)) if mode.traits else list(st.deps)
+            dep_fn = " : ".join(f"d == {d} ? {c}" for d, c in enumerate(deps)) + " : 0"
+            lead = ("grouped single-launch closure kernel (forward streams -> LDS exchange ->\n"
+                    "// per-point stage, one point per lane -> reverse pass)")
+            check = f'static_assert(CFG::NS * CFG::NOUT == {width}, "stream layout of the traced program and of the kernel disagree");\n'
+            pw = f"""struct PW {{
   // NC rows of the coordinate block per point: the batch coordinates, then ND data columns; NT trainable scalars
   static constexpr int NEQ = {neq}, NF = {nf}, ND = {self.n_data}, NT = {self.n_theta}, NC = {self.n_coords} + ND, NR = {self.n_r};
   static constexpr int dep(int d) {{ return {dep_fn}; }}     // batch coordinate fed to network input d
@@ -725,15 +575,37 @@ static_assert(CFG::NS * CFG::NOUT == {width}, "stream layout of the traced progr
     for (int d = 0; d < NC; ++d) c[d] = cc[d];
 #pragma unroll
     for (int j = 0; j < NT; ++j) c[NC + j] = th[j];
-{chr(10).join(loads)}
-    ndq_pw_point(c, s, seed, want_adj, r, f, g);
-    if (!want_adj) return;
-{chr(10).join(stores)}
+"""
+        else:
+            dims = "" if R == 1 else f"[{R}]"
+            head = mode.apply_head.format(jets=f"const float (&jets){dims}[CFG::NS]", gj=f"float (&gj){dims}[CFG::NS]",
+                                          r=f"float (&r)[{self.n_r}]", f=f"float (&f)[{max(nf, 1)}]")
+            lead, check = "single-launch closure kernel (forward streams + pointwise stage +\n// reverse pass)", ""
+            pw = f"""struct PW {{
+  // ND per-point data columns (rows D .. D + ND of the coordinate block), NT trainable scalars of the equations
+  static constexpr int NEQ = {neq}, NF = {nf}, NR = {self.n_r}, ND = {self.n_data}, NT = {self.n_theta};
+  static __device__ __forceinline__ float loss(const float* r) {{ return ndq_pw_loss(r); }}
+{head}
+    float c[CFG::D + ND + NT], s[{nsym}], g[{nsym} + NT];
 #pragma unroll
-    for (int j = 0; j < NT; ++j) gth[j] = g[{len(self.symbols)} + j];
-  }}
-}};
-{host}"""
+    for (int d = 0; d < CFG::D; ++d) c[d] = x[d];
+#pragma unroll
+    for (int j = 0; j < ND + NT; ++j) c[CFG::D + j] = xe[j];
+"""
+        # hidden-layer weight gradients from the bf16x3 planes through transposing LDS reads (csrc/ndq_mlp.h Cfg::WG_TR; shapes
+        # it does not cover, or whose R images would not fit the LDS, ignore the switch).  NDQ_WG_TR_K: weight images in LDS --
+        # one per row, a network with two sites is staged twice
+        wg_tr = f"#ifndef NDQ_WG_TR\n#define NDQ_WG_TR 1\n#endif\n#define NDQ_WG_TR_K {R}\n" if mode.wg_tr else ""
+        return f"""// GENERATED by neurodiffeq_amd/codegen.py -- {lead} of one PDE system{mode.what.format(N=N, R=R)}, gfx950.
+{wg_tr}{CLOSURE_PRODUCTS if mode.products else ""}#include "{mode.header}"
+#define NDQ_PW_INLINE __device__ __forceinline__
+#ifndef NDQ_MAX_BLOCKS
+#define NDQ_MAX_BLOCKS 256     // closure workgroups per launch {mode.blocks_note}
+#endif
+{self.point_fn_source()}
+namespace {{
+using CFG = {mode.cfg(desc)};
+{check}{self._site_traits() if mode.traits else ""}{pw}{point}{_closure_host(mode, N, R, f64)}"""
 
     def _emit(self):
         nsym = max(len(self.symbols), 1)
@@ -1333,7 +1205,8 @@ def mlp_ext_module(desc, f64=False):
 def can_fuse_f64(program, descs):
     """fp64 systems: the single-launch closure exists for ONE network on the plain closure kernel (no grouped / wide /
     multi-network variant in double)."""
-    return program.n_nets == 1 and can_fuse(program, descs) and fuse_mode(program, descs) == "tile" and descs[0].hidden <= 64
+    mode = fuse_mode(program, descs)        # (one network: of the modes with an fp64 build, only the plain closure can come back)
+    return program.n_nets == 1 and mode is not None and MODES[mode].f64 and descs[0].hidden <= 64
 
 
 def can_fuse_multi_f64(program, descs):
@@ -1343,12 +1216,23 @@ def can_fuse_multi_f64(program, descs):
     module fits the LDS of one workgroup is the engine's question to the built module (``ndq_fused_lds_bytes``).
     ``can_fuse_f64`` keeps its meaning: the one-network closure."""
     K = program.n_nets
-    if not (2 <= K <= 4) or program.n_sites != K or descs is None or fuse_mode(program, descs) != "multi":
+    if not (2 <= K <= 4) or program.n_sites != K or descs is None:
+        return False
+    mode = fuse_mode(program, descs)        # (2..4 networks, as many sites: of the modes with an fp64 build, only "multi")
+    if mode is None or not MODES[mode].f64:
         return False
     d0 = descs[0]
-    if d0.n_out != 1 or d0.mask3 or getattr(d0, "mask4", 0) or d0.skip or d0.actp or d0.mono:
+    if d0.n_out != 1 or _high_order(d0) or d0.skip or d0.actp or d0.mono:
         return False
-    return not any(program.streams[k].mask3 or getattr(program.streams[k], "mask4", 0) for k in range(K))
+    return not any(_high_order(program.streams[k]) for k in range(K))
+
+
+def fused_build_plan(program: PointwiseProgram, desc, threads=None, f64=False, more_flags=()):
+    """What ``build_fused`` compiles, without compiling it: (source, extra hipcc flags, cache key) of the closure module."""
+    source = program.fused_source(desc, f64=f64)
+    flags = (_extra_flags() + list(more_flags) + ([f"-DNDQ_BWD_THREADS={int(threads)}"] if threads else [])
+             + (WIDE_FLAGS if program.closure_mode(desc).wide_flags else []))
+    return source, flags, _cache_key(source + (f"|threads={int(threads)}" if threads else ""), more_flags)
 
 
 def build_fused(program: PointwiseProgram, desc, force=False, threads=None, f64=False, more_flags=()):
@@ -1357,9 +1241,7 @@ def build_fused(program: PointwiseProgram, desc, force=False, threads=None, f64=
     per-wave state fits 256 registers; csrc/ndq_mlp.h NDQ_BWD_THREADS) the engine uses for large batches.
     ``more_flags``: compile flags behind those of NDQ_JIT_FLAGS, as if they had been given there (the same cache entry)."""
     os.makedirs(JIT_DIR, exist_ok=True)
-    source = program.fused_source(desc, f64=f64)
-    flags = _extra_flags() + list(more_flags) + ([f"-DNDQ_BWD_THREADS={int(threads)}"] if threads else []) + (WIDE_FLAGS if is_wide(desc) else [])
-    key = _cache_key(source + (f"|threads={int(threads)}" if threads else ""), more_flags)
+    source, flags, key = fused_build_plan(program, desc, threads, f64, more_flags)
     so = os.path.join(JIT_DIR, f"fused_{key}.so")
     src = os.path.join(JIT_DIR, f"fused_{key}.hip")
     if os.path.exists(so) and not force:
@@ -1371,6 +1253,83 @@ def build_fused(program: PointwiseProgram, desc, force=False, threads=None, f64=
     except RuntimeError as e:
         raise RuntimeError(f"hipcc failed for generated fused kernel {src}:\n{str(e)[-4000:]}") from e
     return so
+
+
+#: What a closure mode is, beyond the rule that selects it (``fuse_mode``): the facts the engine and the build ask about and the
+#: C++ texts its generated module is assembled from (``PointwiseProgram._fused_source``, ``_closure_host``).  In the texts {N} is
+#: the number of parameter sets, {R} the number of stream rows -- networks, or evaluation sites -- and {train} the kernel's mode.
+ClosureMode = namedtuple("ClosureMode", [
+    "header",        # kernel header, found through -I csrc (_hipcc.BASE_FLAGS): sources and cache keys do not depend on the checkout path
+    "rows",          # per-point interface: False = jets[R][NS] / gj arrays, True = srow / grow rows through the LDS exchange
+    "padded_rows",   # rows: a stream's outputs are padded to 16 (ndq::group_w)
+    "traits",        # the module carries the site traits (_site_traits); no pull mode then
+    "wg_tr",         # the preamble sets NDQ_WG_TR / NDQ_WG_TR_K
+    "products",      # the preamble carries CLOSURE_PRODUCTS
+    "off",           # environment variable that turns the mode off, or None
+    "f64",           # a build in double exists
+    "eight_wave",    # an 8-wave build can exist (engine.FusedSystem._wide_possible) ...
+    "eight_wave_opt_in",    # ... only if this environment variable is "1"
+    "wide_flags",    # compiled with WIDE_FLAGS
+    "what", "blocks_note", "apply_head",         # title comment, NDQ_MAX_BLOCKS comment, head of PW::apply (jets)
+    "cfg", "args", "threads", "points", "slots", "kern", "tv", "lds", "loop", "lds_loop", "loop_max"])
+
+_APPLY = """  // xe: the point's ND data values, then the NT scalars;  gth (want_adj): per-point adjoints of the scalars
+  static __device__ __forceinline__ void apply(const float (&x)[CFG::D], const float* xe, {jets}, float seed,
+                                               int want_adj, {r}, {f},
+                                               {gj}, float* gth) {{"""
+_APPLY_SITES = """  // x: the batch point (every site's real inputs);  jets / gj: streams and their adjoints, per SITE
+  static __device__ __forceinline__ void apply(const float (&x)[CFG::D], const float* xe, {jets},
+                                               float seed, int want_adj, {r}, {f},
+                                               {gj}, float* gth) {{"""
+_TILE = ClosureMode(
+    header="ndq_mlp.h", rows=False, padded_rows=False, traits=False, wg_tr=True, products=True, off=None, f64=True,
+    eight_wave=True, eight_wave_opt_in=None, wide_flags=False, what=" with {N} network(s)",
+    blocks_note="(one per CU; experiments: 512 = two 8-wave workgroups per CU)", apply_head=_APPLY,
+    cfg=lambda desc: mlp_cfg(desc, 1), args="FusedArgs", threads="CFG::BWD_THREADS", points="16", slots="CFG::BWD_THREADS / 64",
+    kern="ndq::fused_closure_kernel<CFG, PW, {train}>", tv="ndq::fused_closure_tv_kernel<CFG, PW>",
+    lds="ndq::fused_lds_bytes<CFG>({train})", loop="ndq::fused_closure_loop_kernel<CFG, PW>",
+    lds_loop="ndq::fused_loop_lds_bytes<CFG>()", loop_max=1)
+# workgroup shape: waves x tiles per round (multi-network closure: R x G waves, G tile slots -- csrc/ndq_mlp.h).  No 8-wave
+# build: R x G waves, one per SIMD, whatever the batch size (multi_threads)
+_MULTI = _TILE._replace(
+    off="NDQ_NO_MULTI_FUSE", eight_wave=False, args="FusedMultiArgs", threads="ndq::multi_threads<{R}>()",
+    slots="ndq::multi_group<{R}>()", kern="ndq::fused_multi_closure_kernel<CFG, {R}, PW, {train}>",
+    tv="ndq::fused_multi_closure_tv_kernel<CFG, {R}, PW>", lds="(ndq::fused_multi_lds_bytes<CFG, {R}>({train}))",
+    loop="ndq::fused_multi_closure_loop_kernel<CFG, {R}, PW>", lds_loop="(ndq::fused_multi_loop_lds_bytes<CFG, {R}>())", loop_max=2)
+_GROUP = _TILE._replace(
+    rows=True, padded_rows=True, wg_tr=False, off="NDQ_NO_GROUP_FUSE", f64=False, what="", apply_head=None,
+    eight_wave_opt_in="NDQ_GROUP_WIDE",         # experiment: 8 waves with 32-point groups
+    cfg=lambda desc: mlp_cfg(desc, desc.n_out), points="16 * ndq::group_tiles<CFG>()",
+    kern="ndq::fused_group_closure_kernel<CFG, PW, {train}>", tv="ndq::fused_group_closure_tv_kernel<CFG, PW>",
+    lds="ndq::group_lds_bytes<CFG>({train})", loop=None, lds_loop=None, loop_max=0)
+_WIDE = _GROUP._replace(
+    header="ndq_wide.h", padded_rows=False, off="NDQ_NO_WIDE_FUSE", eight_wave_opt_in=None, wide_flags=True, cfg=lambda desc: wide_cfg(desc),
+    points="16", kern="ndq::wide_closure_kernel<CFG, PW, {train}>", tv="ndq::wide_closure_tv_kernel<CFG, PW>",
+    lds="(ndq::wide_closure_lds_bytes<CFG, PW>())")
+# no 8-wave build: one wave per SIMD holds R networks' accumulators (csrc/ndq_wide.h: NDQ_WIDE_THREADS)
+_WIDE_MULTI = _WIDE._replace(
+    off="NDQ_NO_WIDE_MULTI_FUSE", eight_wave=False, what=" with {R} networks", args="FusedMultiArgs",
+    kern="ndq::wide_multi_closure_kernel<CFG, {R}, PW, {train}>", tv="ndq::wide_multi_closure_tv_kernel<CFG, {R}, PW>",
+    lds="(ndq::wide_multi_closure_lds_bytes<CFG, {R}, PW>())")
+MODES = {
+    "tile": _TILE, "multi": _MULTI, "group": _GROUP, "wide": _WIDE, "wide_multi": _WIDE_MULTI,
+    # R = 2..4 evaluation sites of N networks on R wave groups: stream arrays per site, parameter sets and gradient partials per
+    # network behind the multi-network argument struct (N = 1 included).  No CLOSURE_PRODUCTS: every GEMM keeps all six bf16
+    # plane products.  A network's gradient is the SUM of its sites' and those nearly cancel (u - u(x_b) - w u_x(x_b): the
+    # output bias drops out exactly), so the 4- / 3-product reverse and weight-gradient GEMMs of the other closure modules,
+    # 1e-6 of each site's gradient, come to 1e-5 of the network's (measured: heat equation with two Neumann ends 1.25e-5
+    # against fp64 with them, 2e-7 without); these systems are launch-bound
+    "sites": _MULTI._replace(
+        traits=True, products=False, off="NDQ_NO_SITE_FUSE", f64=False, what=" with {N} network(s) at {R} evaluation sites",
+        blocks_note="(one per CU)", apply_head=_APPLY_SITES, kern="ndq::fused_multi_closure_kernel<CFG, {R}, PW, {train}, SITES>",
+        tv="ndq::fused_multi_closure_tv_kernel<CFG, {R}, PW, SITES>", loop=None, lds_loop=None, loop_max=0),
+    # R slices, N unit images (csrc/ndq_wide.h: wide_multi_closure_body with site traits); parameter sets and gradient
+    # partials per network behind the multi-network argument struct, as the narrow site modules
+    "wide_sites": _WIDE_MULTI._replace(
+        traits=True, off="NDQ_NO_WIDE_SITE_FUSE", what=" with {N} network(s) at {R} evaluation sites",
+        kern="ndq::wide_multi_closure_kernel<CFG, {R}, PW, {train}, SITES>",
+        tv="ndq::wide_multi_closure_tv_kernel<CFG, {R}, PW, SITES>", lds="(ndq::wide_multi_closure_lds_bytes<CFG, {R}, PW, {N}>())"),
+}
 
 
 def fuse_mode(program: PointwiseProgram, descs=None):
@@ -1392,66 +1351,125 @@ def fuse_mode(program: PointwiseProgram, descs=None):
              third- / fourth-order streams (wide_multi_closure_kernel with site traits: one wave runs all sites of a tile
              and sums a network's gradient over its sites in its own registers); NDQ_NO_WIDE_SITE_FUSE is its off-switch.
     None     three-kernel pipeline."""
-    K = program.n_nets
-    if K >= 1 and program.n_sites > K:
-        if descs is not None and 0 in descs and is_wide(descs[0]):
-            return "wide_sites" if _sites_ok(program, descs, wide=True) else None
-        return "sites" if _sites_ok(program, descs) else None
-    if K < 1 or K > 4 or program.n_sites != K or any(k not in program.streams for k in range(K)):
+    K, S, nc = program.n_nets, program.n_sites, program.n_coords
+    d0 = descs[0] if descs is not None and 0 in descs else None
+    if K >= 1 and S > K:
+        wide = d0 is not None and is_wide(d0)
+        if not _sites_ok(program, descs) or _switched_off("wide_sites" if wide else "sites"):
+            return None
+        if wide:
+            return "wide_sites" if _wide_one_layer(d0.hidden, d0.layers, d0.skip, d0.actp, d0.mono) else None
+        return "sites" if _fits_multi(d0.hidden) else None
+    if K < 1 or K > 4 or S != K or any(k not in program.streams for k in range(K)):
         return None
-    plain = all(tuple(program.streams[k].deps) == tuple(range(program.n_coords)) and program.streams[k].n_out == 1
-                for k in range(K))
+    streams = [program.streams[k] for k in range(K)]
+    plain = all(tuple(st.deps) == tuple(range(nc)) and st.n_out == 1 for st in streams)
+    batch_inputs = all(c < nc for c in streams[0].deps)       # network 0 reads batch coordinates only, any subset of them
     if K == 1:
-        st = program.streams[0]
-        d0 = descs[0] if descs is not None and 0 in descs else None
         if d0 is not None and is_wide(d0):
             # one hidden layer wider than 64 units: csrc/ndq_wide.h's closure kernel (any number of outputs, any subset of
             # the batch coordinates as inputs)
-            return "wide" if (d0.layers == 1 and all(c < program.n_coords for c in st.deps)
-                              and not os.environ.get("NDQ_NO_WIDE_FUSE")) else None
-        group_ok = (d0 is not None and padded_width(d0.hidden) <= 48 and all(c < program.n_coords for c in st.deps)
-                    and not os.environ.get("NDQ_NO_GROUP_FUSE"))
-        if plain and not (group_ok and os.environ.get("NDQ_FUSE_GROUP") == "1"):
+            return "wide" if (d0.layers == 1 and batch_inputs and not _switched_off("wide")) else None
+        group_ok = d0 is not None and _fits_multi(d0.hidden) and batch_inputs and not _switched_off("group")
+        if plain and not (group_ok and os.environ.get("NDQ_FUSE_GROUP") == "1"):     # (the redirect takes PLAIN systems too)
             return "tile"
         return "group" if group_ok else None
     if descs is not None and all(k in descs for k in range(K)) and any(is_wide(descs[k]) for k in range(K)):
-        d0, deps = descs[0], tuple(program.streams[0].deps)
-        ok = (len({descs[k].key() for k in range(K)}) == 1 and d0.layers == 1 and not (d0.skip or d0.actp or d0.mono)
-              and all(c < program.n_coords for c in deps) and all(tuple(program.streams[k].deps) == deps for k in range(K))
-              and not os.environ.get("NDQ_NO_WIDE_MULTI_FUSE"))
+        # (one descriptor, so network 0's width is every network's; no descriptor exceeds MAX_HIDDEN)
+        ok = (_one_shape(descs, K) and _wide_one_layer(d0.hidden, d0.layers, d0.skip, d0.actp, d0.mono) and batch_inputs
+              and all(tuple(st.deps) == tuple(streams[0].deps) for st in streams) and not _switched_off("wide_multi"))
         return "wide_multi" if ok else None
     if not plain:
         return None
-    if descs is None or len({descs[k].key() for k in range(K)}) != 1 or padded_width(descs[0].hidden) > 48:
+    if descs is None or not _one_shape(descs, K) or not _fits_multi(descs[0].hidden):
         return None
-    if os.environ.get("NDQ_NO_MULTI_FUSE"):
-        return None
-    return "multi"
+    return None if _switched_off("multi") else "multi"
 
 
-def _sites_ok(program, descs, wide=False):
-    """``fuse_mode``: may the evaluation-site closure kernel serve this system?  (``wide``: the one of csrc/ndq_wide.h)"""
-    S, nc = program.n_sites, program.n_coords
-    off = "NDQ_NO_WIDE_SITE_FUSE" if wide else "NDQ_NO_SITE_FUSE"
-    if not (2 <= S <= 4) or os.environ.get(off) or any(k not in program.streams for k in range(S)):
+def _sites_ok(program, descs):
+    """``fuse_mode``: what both evaluation-site closure kernels ask of a system, whatever the width of its networks.
+    (fp64 systems never get here with a say: the modes with sites have no fp64 build.)"""
+    S = program.n_sites
+    if not (2 <= S <= 4) or any(k not in program.streams for k in range(S)):
         return False
-    if descs is None or any(k not in descs for k in range(S)) or len({descs[k].key() for k in range(S)}) != 1:
+    if descs is None or any(k not in descs for k in range(S)) or not _one_shape(descs, S):
         return False
-    d0 = descs[0]
-    if wide:
-        if not is_wide(d0) or d0.hidden > 512 or d0.layers != 1 or d0.skip or d0.actp or d0.mono:
-            return False
-    elif is_wide(d0) or padded_width(d0.hidden) > 48:
+    if descs[0].n_out != 1 or _high_order(descs[0]):
         return False
-    if d0.n_out != 1 or d0.mask3 or getattr(d0, "mask4", 0):
-        return False
-    for k in range(S):               # (fp64 systems never get here with a say: can_fuse_f64 takes "tile" only)
-        st = program.streams[k]
-        if st.n_out != 1 or st.mask3 or getattr(st, "mask4", 0) or len(st.deps) != nc:
-            return False
-        if any(c != a and c not in program.g.vcoords for a, c in enumerate(st.deps)):
-            return False              # entry a of a site's inputs: batch coordinate a, or a boundary value
-    return True
+    return all(st.n_out == 1 and not _high_order(st) and _site_inputs(st.deps, program.n_coords, program.g.vcoords)
+               for st in (program.streams[k] for k in range(S)))
+
+
+# ---- the conditions the rules above and ``unify`` share, each stated once
+def _switched_off(name):
+    """Is closure mode ``name`` turned off by its environment variable?"""
+    off = MODES[name].off
+    return bool(off and os.environ.get(off))
+
+
+def _one_shape(descs, n):
+    """Do sites 0 .. n-1 have ONE descriptor (network shape and stream set)?"""
+    return len({descs[k].key() for k in range(n)}) == 1
+
+
+def _fits_multi(hidden):
+    """The narrow multi-row kernels (multi, sites, group) hold their weight images in LDS: padded width up to 48."""
+    return padded_width(hidden) <= 48
+
+
+def _wide_one_layer(hidden, layers, skip, actp, mono):
+    """What csrc/ndq_wide.h's multi-row closure kernels take: ONE hidden layer of 65 .. 512 units, plain FCNN."""
+    return 64 < hidden <= MAX_HIDDEN and layers == 1 and not (skip or actp or mono)
+
+
+def _high_order(st):
+    """Third- or fourth-order streams in a stream set (``NetStreams``) or a descriptor."""
+    return bool(st.mask3 or getattr(st, "mask4", 0))
+
+
+def _site_inputs(deps, n_coords, vcoords):
+    """Entry a of an evaluation site's inputs: batch coordinate a, or a boundary value."""
+    return len(deps) == n_coords and all(c == a or c in vcoords for a, c in enumerate(deps))
+
+
+def unify(streams, site_net, n_coords, vcoords, infos, f64):
+    """The ``unify`` hook of ``PointwiseProgram``.  2..4 networks of ONE shape reading all coordinates: give them the union
+    of their stream sets, so that the multi-network closure kernel (one launch for the whole system) can serve them; a network
+    then carries at most a few streams it does not need -- these systems are launch-bound, not compute-bound.  The same for
+    2..4 evaluation sites of fewer networks ("sites", "wide_sites"): every site reads all batch coordinates, some replaced by
+    a boundary value -- stream sets are per input POSITION.  streams: {site: NetStreams}; infos: ``networks.describe`` per network.
+    It decides BEFORE the descriptors exist what ``fuse_mode`` decides after them, from the same predicates.  Kept as they are:
+    fp64 leaves site systems alone (no fp64 build with sites) but unifies plain multi-network ones (``can_fuse_multi_f64``, which
+    NDQ_NO_MULTI_FUSE turns off with the fp32 mode); the wide-site test here also asks for ``widths == 0``; wide networks
+    WITHOUT sites ("wide_multi") are not unified, their width fails ``_fits_multi``."""
+    K, S, i0 = len(infos), len(site_net), infos[0]
+    wide_sites = (S > K and _wide_one_layer(i0["hidden"], i0["layers"], i0["skip"], i0["actp"], i0["mono"])
+                  and not i0["widths"])
+    if S > K:
+        if not (2 <= S <= 4) or len(streams) != S or f64 or _switched_off("wide_sites" if wide_sites else "sites"):
+            return
+        if not all(_site_inputs(st.deps, n_coords, vcoords) for st in streams.values()):
+            return
+    elif not (2 <= K <= 4) or len(streams) != K or _switched_off("multi"):
+        return
+    shape = {(i["d"], i["hidden"], i["layers"], i["act"], i["n_out"], i["skip"], i["actp"], i["widths"], i["mono"]) for i in infos}
+    if len(shape) != 1 or i0["n_out"] != 1 or not (wide_sites or _fits_multi(i0["hidden"])):
+        return
+    if S == K and any(tuple(st.deps) != tuple(range(n_coords)) for st in streams.values()):
+        return
+    sts = list(streams.values())
+    if any(_high_order(st) for st in sts):
+        return              # third- / fourth-order stream sets are served network by network (three-kernel pipeline)
+    if len({(st.first, st.mask2, st.lap) for st in sts}) == 1:
+        return
+    lap = max(st.lap for st in sts)
+    if lap and any((not st.lap) and st.mask2 for st in sts):
+        return              # some network needs its second derivatives one by one, another only their sum
+    first, mask2 = max(st.first for st in sts), 0
+    for st in sts:
+        mask2 |= st.mask2
+    for st in sts:
+        st.first, st.mask2, st.lap = first, mask2, lap
 
 
 def can_fuse(program: PointwiseProgram, descs=None):

@@ -11,6 +11,7 @@ fixed launch sequence on one HIP stream, per batch:
 No host synchronisation happens inside a step; the loss stays in HBM until the caller reads it.
 """
 import ctypes
+import functools
 import os
 
 import torch
@@ -324,46 +325,8 @@ def trace_system(nets, conditions, diff_eqs, n_coords, compute_func_val=None, lo
         st.first, st.mask2 = best[1].first, best[1].mask2
         descs[k] = best[1]
 
-    def unify(streams):
-        """2..4 networks of ONE shape reading all coordinates: give them the union of their stream sets, so that the
-        multi-network closure kernel (one launch for the whole system) can serve them; a network then carries at most
-        a few streams it does not need -- these systems are launch-bound, not compute-bound."""
-        K = len(nets)
-        S = len(g.site_net)
-        i0 = infos[0]
-        # sites of networks with one hidden layer of 65 .. 512 units: codegen.fuse_mode "wide_sites", a switch of its own
-        wide_sites = (S > K and i0["layers"] == 1 and 64 < i0["hidden"] <= 512
-                      and not (i0["skip"] or i0["actp"] or i0["mono"] or i0["widths"]))
-        if S > K:
-            # ... and the same for 2..4 evaluation sites of fewer networks (Neumann ends: codegen.fuse_mode "sites"): every
-            # site reads all batch coordinates, some replaced by a boundary value -- stream sets are per input POSITION
-            off = "NDQ_NO_WIDE_SITE_FUSE" if wide_sites else "NDQ_NO_SITE_FUSE"
-            if not (2 <= S <= 4) or len(streams) != S or f64 or os.environ.get(off):
-                return
-            if any(len(st.deps) != n_coords or any(c != a and c not in g.vcoords for a, c in enumerate(st.deps))
-                   for st in streams.values()):
-                return
-        elif not (2 <= K <= 4) or len(streams) != K or os.environ.get("NDQ_NO_MULTI_FUSE"):
-            return
-        shape = {(i["d"], i["hidden"], i["layers"], i["act"], i["n_out"], i["skip"], i["actp"], i["widths"], i["mono"]) for i in infos}
-        if len(shape) != 1 or infos[0]["n_out"] != 1 or (codegen.padded_width(infos[0]["hidden"]) > 48 and not wide_sites):
-            return
-        if S == K and any(tuple(st.deps) != tuple(range(n_coords)) for st in streams.values()):
-            return
-        sts = list(streams.values())
-        if any(st.mask3 or getattr(st, "mask4", 0) for st in sts):
-            return              # third- / fourth-order stream sets are served network by network (three-kernel pipeline)
-        if len({(st.first, st.mask2, st.lap) for st in sts}) == 1:
-            return
-        lap = max(st.lap for st in sts)
-        if lap and any((not st.lap) and st.mask2 for st in sts):
-            return              # some network needs its second derivatives one by one, another only their sum
-        first, mask2 = max(st.first for st in sts), 0
-        for st in sts:
-            mask2 |= st.mask2
-        for st in sts:
-            st.first, st.mask2, st.lap = first, mask2, lap
-
+    # (which systems get one common stream set is the code generator's question: it knows the closure kernels' rules)
+    unify = functools.partial(codegen.unify, site_net=g.site_net, n_coords=n_coords, vcoords=g.vcoords, infos=infos, f64=f64)
     program = codegen.PointwiseProgram(g, [r.i for r in res],
                                        [c.i for cols in func_columns for c in cols] + [m.i for m in metric_terms],
                                        len(nets), widen=widen, allow_lap=allow_lap, unify=unify, loss=loss,
@@ -562,13 +525,11 @@ class FusedSystem:
     def _wide_possible(self):
         """Does csrc/ndq_mlp.h give this shape an 8-wave build at all?  (Cfg::BWD_THREADS: per-wave state of more than 40
         fragment blocks keeps the whole register file, i.e. 4 waves -- no point compiling to find that out)"""
-        mode = codegen.fuse_mode(self.program, self.descs)
-        if mode in ("multi", "sites"):
-            return False            # K x G waves, one per SIMD, whatever the batch size (csrc/ndq_mlp.h: multi_threads)
-        if mode in ("wide_multi", "wide_sites"):
-            return False            # one wave per SIMD holds K networks' accumulators (csrc/ndq_wide.h: NDQ_WIDE_THREADS)
-        if mode == "group":
-            return os.environ.get("NDQ_GROUP_WIDE", "0") == "1"     # experiment: 8 waves with 32-point groups
+        mode = codegen.MODES.get(codegen.fuse_mode(self.program, self.descs))
+        if mode is not None and not mode.eight_wave:
+            return False            # (the multi-row kernels: codegen.MODES says why)
+        if mode is not None and mode.eight_wave_opt_in:
+            return os.environ.get(mode.eight_wave_opt_in, "0") == "1"
         d = self.descs[0]
         nb, layers = (d.hidden + 15) // 16, d.layers
         ns = self.L.ndq_mlp_num_streams(ctypes.byref(d))
