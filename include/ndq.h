@@ -434,6 +434,40 @@ int ndq64_epoch_tail(double* params, const double* grad, double* exp_avg, double
                      int n_batches, double* loss_hist, int hist_index, double* best_loss, int parity, double* best_flat,
                      int write_scalars, void* stream);
 
+/* ndq_fused_launch_multi of a closure module generated in double (every module, one network included, exports it). */
+typedef int (*ndq64_fused_launch_multi_fn)(const double* coords, int ldc, int n, const double* const* params,
+                                           double* const* partials, double* loss_partials, double* funcs, double* resid,
+                                           int ldj, double seed, int train, void* stream);
+/* ndq_fused_step in double: what one training epoch (one batch) of network k of an fp64 system behind ONE closure launch
+ * needs.  No launcher member (ndq64_fused_step_run takes the module's multi-network launcher), no data-parallel hook, no
+ * device prefetch.  n / ldc / ldj / blocks / seed / loss_partials / loss_hist / best_loss are read from steps[0]. */
+typedef struct ndq64_fused_step {
+  int n, ldc, ldj, blocks, n_params;
+  double seed;                /* 1 / (N * n_eq) */
+  double* params;             /* [P] */
+  double* partials;           /* [blocks][P] */
+  double* loss_partials;      /* [blocks] */
+  double* grad;               /* [P] */
+  double* loss_slot;          /* [1] */
+  double* adam_m;             /* [P] */
+  double* adam_v;             /* [P] */
+  double lr, beta1, beta2, eps, weight_decay;
+  double* loss_hist;          /* ring of epoch losses */
+  double* best_loss;          /* [2] */
+  double* best_flat;          /* [P]  (NULL: no snapshot) */
+} ndq64_fused_step;
+/* sizeof(ndq64_fused_step): lets a binding check its mirror of the struct without a GPU */
+int ndq64_fused_step_bytes(void);
+/* The sums + tail launch of an fp64 epoch alone, for n_nets = 1..4 networks in ONE launch: second-stage sums of every
+ * network's gradient partial rows [blocks][P_k] and of the loss partials [blocks], loss -> loss_slot and
+ * loss_hist[hist_index], best-loss ping-pong (read best_loss[parity], write best_loss[parity ^ 1]) + snapshot of the
+ * pre-update parameters, Adam.  Bit for bit what ndq64_reduce_partials (gradient of every network; loss partials with
+ * len = 1, scale = seed) followed by ndq64_epoch_tail per network leave behind.  Network 0 writes the scalars. */
+int ndq64_reduce_tail(const ndq64_fused_step* steps, int n_nets, int adam_step, int hist_index, int parity, void* stream);
+/* A whole fp64 training epoch from one native call: the closure launch, then ndq64_reduce_tail.  Two launches. */
+int ndq64_fused_step_run(const ndq64_fused_step* steps, int n_nets, ndq64_fused_launch_multi_fn launch,
+                         const double* coords, int adam_step, int hist_index, int parity, void* stream);
+
 /* ---- one-shot all-reduce of the small [gradient | loss] message (data-parallel training) ------------
  * Every rank writes its vector straight into every peer's inbox (fine-grained device memory shared through HIP IPC; on
  * MI355X one xGMI hop to each of the 7 peers) and adds up the world_size vectors it received, in rank order: ONE

@@ -93,6 +93,18 @@ class FusedStep(ctypes.Structure):
                 ("next_stream", ctypes.c_uint), ("next_coords", ctypes.c_void_p), ("next_ldc", ctypes.c_int)]
 
 
+class FusedStep64(ctypes.Structure):
+    """ndq64_fused_step of include/ndq.h"""
+    _fields_ = [("n", ctypes.c_int), ("ldc", ctypes.c_int), ("ldj", ctypes.c_int), ("blocks", ctypes.c_int),
+                ("n_params", ctypes.c_int), ("seed", ctypes.c_double),
+                ("params", ctypes.c_void_p), ("partials", ctypes.c_void_p), ("loss_partials", ctypes.c_void_p),
+                ("grad", ctypes.c_void_p), ("loss_slot", ctypes.c_void_p), ("adam_m", ctypes.c_void_p),
+                ("adam_v", ctypes.c_void_p),
+                ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double),
+                ("loss_hist", ctypes.c_void_p), ("best_loss", ctypes.c_void_p), ("best_flat", ctypes.c_void_p)]
+
+
 class FusedFit(ctypes.Structure):
     """ndq_fused_fit of include/ndq.h"""
     _fields_ = [("launch", ctypes.c_void_p), ("n_nets", ctypes.c_int), ("net", FusedStep * 4),
@@ -191,6 +203,9 @@ def lib64():
     cd = ctypes.c_double
     L.ndq64_adam_step.argtypes = [vp, vp, vp, vp, ci, cd, cd, cd, cd, cd, ci, vp]
     L.ndq64_epoch_tail.argtypes = [vp, vp, vp, vp, ci, cd, cd, cd, cd, cd, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp]
+    L.ndq64_fused_step_bytes.argtypes = []
+    L.ndq64_reduce_tail.argtypes = [ctypes.POINTER(FusedStep64), ci, ci, ci, ci, vp]
+    L.ndq64_fused_step_run.argtypes = [ctypes.POINTER(FusedStep64), ci, vp, vp, ci, ci, ci, vp]
     for name in EXPORTS64:
         getattr(L, name).restype = ci
     _LIB64 = L
@@ -199,7 +214,7 @@ def lib64():
 
 EXPORTS64 = ("ndq64_mlp_register", "ndq64_mlp_supported", "ndq64_mlp_num_streams", "ndq64_mlp_num_params",
              "ndq64_mlp_bwd_blocks", "ndq64_mlp_jet_fwd", "ndq64_mlp_jet_bwd", "ndq64_reduce_partials", "ndq64_adam_step",
-             "ndq64_epoch_tail")
+             "ndq64_epoch_tail", "ndq64_fused_step_bytes", "ndq64_reduce_tail", "ndq64_fused_step_run")
 
 EXPORTS = ("ndq_mlp_supported", "ndq_mlp_num_streams", "ndq_mlp_num_params", "ndq_mlp_bwd_blocks", "ndq_mlp_jet_fwd",
            "ndq_mlp_jet_bwd", "ndq_reduce_partials", "ndq_adam_step", "ndq_reduce_grad_loss", "ndq_epoch_tail",

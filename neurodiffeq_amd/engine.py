@@ -353,6 +353,14 @@ def wants_closure(program, descs, f64):
     return codegen.can_fuse_f64(program, descs) or codegen.can_fuse_multi_f64(program, descs)
 
 
+def f64_fused_tail_switch(environ=None):
+    """NDQ_F64_FUSED_TAIL=1 (opt-in; unset, "0" or anything else: off): fp64 systems behind a closure kernel finish a training
+    epoch with ONE sums + tail launch in double (``ndq64_fused_step_run``) instead of 1 + 2 K launches.
+    A pure function of the mapping it is given (default: the process environment)."""
+    environ = os.environ if environ is None else environ
+    return environ.get("NDQ_F64_FUSED_TAIL", "0") == "1"
+
+
 class FusedSystem:
     def __init__(self, nets, conditions, diff_eqs, n_coords, device, compute_func_val=None, single_kernel=True,
                  loss="l2", metrics=(), dtype=torch.float32, volatile=frozenset()):
@@ -366,13 +374,15 @@ class FusedSystem:
         # (libndq64.so) with the generated pointwise kernel compiled in double; single-network systems on the plain closure
         # kernel get that kernel compiled in double as well (codegen.can_fuse_f64), systems of 2..4 narrow networks the
         # multi-network closure kernel (codegen.can_fuse_multi_f64); the epoch tail runs on the device
-        # (ndq64_epoch_tail); pull / loop mode, the multi-epoch fit() call and the 8-wave build are fp32 only
+        # (ndq64_epoch_tail; opt-in, NDQ_F64_FUSED_TAIL=1: sums and tail in ONE launch, ndq64_fused_step_run); pull / loop mode,
+        # the multi-epoch fit() call and the 8-wave build are fp32 only
         from . import _canary
         _canary.check()              # once per process: the gfx950 hazard reproducer through / without the assembly fix-up pass
         self.dt = dtype
         self.f64 = dtype == torch.float64
         self.esize = 8 if self.f64 else 4
         self.L = _Lib64() if self.f64 else _lib.lib()
+        self.f64_fused_tail = self.f64 and f64_fused_tail_switch()      # read once, here (f64_tail_ready)
         self.nets, self.conditions, self.n_coords = list(nets), list(conditions), n_coords
         self.program, self.descs = trace_system(self.nets, self.conditions, diff_eqs, n_coords, compute_func_val, loss,
                                                 metrics, f64=self.f64, volatile=volatile)
@@ -1021,8 +1031,16 @@ class FusedSystem:
         for one network only)"""
         return self.fusedk is not None and (len(self.nets) == 1 or dist is None) and not self.f64 and not self.n_theta
 
+    def f64_tail_ready(self):
+        """Can a training epoch of this fp64 system (one batch, no data-parallel shard, all networks at one Adam step -- the
+        caller's part of the condition) go through ``ndq64_fused_step_run``: the closure launch + ONE sums / tail launch in
+        double?  Opt-in (NDQ_F64_FUSED_TAIL=1 when the system was built); ``fast_ready()`` keeps its meaning."""
+        return self.f64 and self.f64_fused_tail and self.fusedk is not None and not self.n_theta
+
     def launches_per_step(self):
         """Kernel launches of one native training epoch with one batch (bench.py reports it per config)."""
+        if self.f64_tail_ready():
+            return 2                                     # closure kernel + ONE sums/tail kernel in double (all networks)
         if self.fusedk is not None and self.f64:
             # closure kernel, loss sum; per network: gradient sum, epoch tail (in double) -- 4 for one network, 6 for two
             return 2 + 2 * len(self.flat)
@@ -1061,7 +1079,7 @@ class FusedSystem:
         st.n, st.ldc, st.ldj, st.blocks, st.n_params = n, ld, ld, blocks, fp.numel
         if partials is not None:
             st.partials, st.loss_partials = partials.data_ptr(), loss_partials.data_ptr()
-        st.grad, st.loss_slot = fp.grad.data_ptr(), fp.grad_loss.data_ptr() + 4 * fp.numel
+        st.grad, st.loss_slot = fp.grad.data_ptr(), fp.grad_loss.data_ptr() + self.esize * fp.numel
         st.loss_hist, st.best_loss = fs["loss_hist"].data_ptr(), fs["best_loss"].data_ptr()
 
     @staticmethod
@@ -1129,6 +1147,36 @@ class FusedSystem:
         rc = self.L.ndq_fused_multi_step_run(arr, K, _c_vp(b["fused_launch_multi"]), self._coord_ptr(b, 0), step,
                                              fs["pending"], fs["parity"], self._stream())
         _lib.check(rc, "ndq_fused_multi_step_run")
+        fs["pending"] += 1
+        fs["parity"] ^= 1
+
+    def fast_train_epoch_f64(self, batch, adam_slots, track_best):
+        """fast_train_epoch_multi in double, for 1..4 networks (``f64_tail_ready``): the closure kernel, then ONE sums + tail
+        kernel for all networks, from one native call (ndq64_fused_step_run).  Leaves, bit for bit, what step() + epoch_tail()
+        leave -- the loss in ``loss_buf[0]`` included."""
+        fs = self.fast_state()
+        b, n = self.upload(batch)
+        K = len(self.flat)
+        key = (n, b["ld"], id(b), "f64")
+        arr = fs["structs"].get(key)
+        if arr is None:
+            arr = (_lib.FusedStep64 * K)()
+            for k in range(K):
+                self._fill_step(arr[k], k, n, b["ld"], b["fused_blocks"], b["fused_partials_all"][k], b["fused_loss_partials"])
+            fs["structs"][key] = arr
+        step = adam_slots[0][3]
+        for k, fp in enumerate(self.flat):
+            fp.sync()
+            m, v, group, _ = adam_slots[k]
+            st = arr[k]
+            st.params = fp.flat.data_ptr()
+            st.seed = 1.0 / (float(n) * self.loss_norm)
+            st.loss_slot = self.loss_buf.data_ptr()      # (where the parent's route keeps the epoch loss of batch 0)
+            st.best_flat = fs["best_flat"][k].data_ptr() if track_best else None
+            self._set_adam(st, m, v, group)
+        rc = self.L.ndq_fused_step_run(arr, K, _c_vp(b["fused_launch_multi"]), self._coord_ptr(b, 0), step, fs["pending"],
+                                       fs["parity"], self._stream())
+        _lib.check(rc, "ndq64_fused_step_run")
         fs["pending"] += 1
         fs["parity"] ^= 1
 
