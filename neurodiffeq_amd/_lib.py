@@ -121,6 +121,34 @@ class NdqError(RuntimeError):
     pass
 
 
+REAL = object()         # placeholder in SHARED_ARGTYPES: c_float in libndq.so, c_double in libndq64.so
+_vp, _ci, _dp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(MlpDesc)
+#: the entry points both libraries have (ndq_<suffix> / ndq64_<suffix>, csrc/ndq_api_common.h and the two sums): suffix -> argtypes
+SHARED_ARGTYPES = {
+    "mlp_supported": [_dp],
+    "mlp_num_streams": [_dp],
+    "mlp_num_params": [_dp],
+    "mlp_bwd_blocks": [_dp, _ci],
+    "mlp_jet_fwd": [_dp, _vp, _ci, _ci, _vp, _vp, _ci, _vp],
+    "mlp_jet_bwd": [_dp, _vp, _ci, _ci, _vp, _vp, _ci, _vp, _vp],
+    "mlp_register": [_vp],
+    "reduce_partials": [_vp, _ci, _ci, _vp, _ci, REAL, _vp],
+    "adam_step": [_vp, _vp, _vp, _vp, _ci, REAL, REAL, REAL, REAL, REAL, _ci, _vp],
+    "epoch_tail": [_vp, _vp, _vp, _vp, _ci, REAL, REAL, REAL, REAL, REAL, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp],
+}
+
+
+def _bind(L, prefix, real, own, exports):
+    """argtypes of the shared entry points (REAL -> ``real``) and of the library's ``own`` ones; every export returns int."""
+    for suffix, args in SHARED_ARGTYPES.items():
+        getattr(L, prefix + suffix).argtypes = [real if a is REAL else a for a in args]
+    for name, args in own.items():
+        getattr(L, name).argtypes = args
+    for name in exports:
+        getattr(L, name).restype = _ci
+    return L
+
+
 _LIB = None
 
 
@@ -136,43 +164,24 @@ def lib():
         except Exception as e:  # no hipcc / compile error
             if not os.path.exists(path):
                 raise NdqError(f"libndq.so is missing and could not be built: {e}") from e
-    L = ctypes.CDLL(path)
-    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    dp = ctypes.POINTER(MlpDesc)
-    L.ndq_mlp_supported.argtypes = [dp]
-    L.ndq_mlp_num_streams.argtypes = [dp]
-    L.ndq_mlp_num_params.argtypes = [dp]
-    L.ndq_mlp_bwd_blocks.argtypes = [dp, ci]
-    L.ndq_mlp_jet_fwd.argtypes = [dp, vp, ci, ci, vp, vp, ci, vp]
-    L.ndq_mlp_jet_bwd.argtypes = [dp, vp, ci, ci, vp, vp, ci, vp, vp]
-    L.ndq_reduce_partials.argtypes = [vp, ci, ci, vp, ci, cf, vp]
-    L.ndq_adam_step.argtypes = [vp, vp, vp, vp, ci, cf, cf, cf, cf, cf, ci, vp]
-    L.ndq_reduce_grad_loss.argtypes = [vp, ci, ci, vp, ci, vp, ci, vp, cf, vp]
-    L.ndq_epoch_tail.argtypes = [vp, vp, vp, vp, ci, cf, cf, cf, cf, cf, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp]
-    L.ndq_fused_step_run.argtypes = [ctypes.POINTER(FusedStep), vp, ci, ci, ci, vp]
-    L.ndq_fused_multi_step_run.argtypes = [ctypes.POINTER(FusedStep), ci, vp, vp, ci, ci, ci, vp]
-    L.ndq_fused_fit_run.argtypes = [ctypes.POINTER(FusedFit), ci, vp, ci, ci, ci, ci, vp]
-    L.ndq_mlp_register.argtypes = [vp]
-    L.ndq_sample.argtypes = [ctypes.POINTER(SamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci, vp]
-    L.ndq_sample_table.argtypes = [ctypes.POINTER(TableSamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci,
-                                   vp]
-    L.ndq_sample_plan.argtypes = [ctypes.POINTER(PlanSamplerDesc), ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, vp, ci, vp]
-    L.ndq_sample_plan_indexed.argtypes = [ctypes.POINTER(PlanSamplerDesc), ctypes.POINTER(PlanIndexDesc), ctypes.c_ulonglong,
-                                          ctypes.c_ulonglong, ctypes.c_uint, vp, ci, vp]
-    L.ndq_oneshot_create.argtypes = [ci, ci, ci, ctypes.POINTER(vp), ctypes.c_char_p]
-    L.ndq_oneshot_connect.argtypes = [vp, ctypes.c_char_p]
-    L.ndq_oneshot_allreduce.argtypes = [vp, vp, ctypes.c_size_t, ci, ci, vp, vp]
-    L.ndq_oneshot_status.argtypes = [vp]
-    L.ndq_oneshot_destroy.argtypes = [vp]
-    for name in ("ndq_mlp_supported", "ndq_mlp_num_streams", "ndq_mlp_num_params", "ndq_mlp_bwd_blocks",
-                 "ndq_mlp_jet_fwd", "ndq_mlp_jet_bwd", "ndq_reduce_partials", "ndq_adam_step", "ndq_reduce_grad_loss",
-                 "ndq_epoch_tail", "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_sample_plan", "ndq_sample_plan_indexed", "ndq_mlp_register",
-                 "ndq_fused_multi_step_run", "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect",
-                 "ndq_oneshot_allreduce", "ndq_oneshot_status",
-                 "ndq_oneshot_destroy"):
-        getattr(L, name).restype = ci
-    _LIB = L
-    return L
+    vp, ci, cf, u64 = _vp, _ci, ctypes.c_float, ctypes.c_ulonglong
+    _LIB = _bind(ctypes.CDLL(path), "ndq_", cf, {
+        "ndq_reduce_grad_loss": [vp, ci, ci, vp, ci, vp, ci, vp, cf, vp],
+        "ndq_fused_step_run": [ctypes.POINTER(FusedStep), vp, ci, ci, ci, vp],
+        "ndq_fused_multi_step_run": [ctypes.POINTER(FusedStep), ci, vp, vp, ci, ci, ci, vp],
+        "ndq_fused_fit_run": [ctypes.POINTER(FusedFit), ci, vp, ci, ci, ci, ci, vp],
+        "ndq_sample": [ctypes.POINTER(SamplerDesc), u64, u64, ctypes.c_uint, vp, ci, vp],
+        "ndq_sample_table": [ctypes.POINTER(TableSamplerDesc), u64, u64, ctypes.c_uint, vp, ci, vp],
+        "ndq_sample_plan": [ctypes.POINTER(PlanSamplerDesc), u64, u64, ctypes.c_uint, vp, ci, vp],
+        "ndq_sample_plan_indexed": [ctypes.POINTER(PlanSamplerDesc), ctypes.POINTER(PlanIndexDesc), u64, u64, ctypes.c_uint, vp, ci,
+                                    vp],
+        "ndq_oneshot_create": [ci, ci, ci, ctypes.POINTER(vp), ctypes.c_char_p],
+        "ndq_oneshot_connect": [vp, ctypes.c_char_p],
+        "ndq_oneshot_allreduce": [vp, vp, ctypes.c_size_t, ci, ci, vp, vp],
+        "ndq_oneshot_status": [vp],
+        "ndq_oneshot_destroy": [vp],
+    }, EXPORTS)
+    return _LIB
 
 
 _LIB64 = None
@@ -189,27 +198,13 @@ def lib64():
         except Exception as e:  # no hipcc / compile error
             if not os.path.exists(_build.LIB64):
                 raise NdqError(f"libndq64.so is missing and could not be built: {e}") from e
-    L = ctypes.CDLL(_build.LIB64)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    dp = ctypes.POINTER(MlpDesc)
-    L.ndq64_mlp_supported.argtypes = [dp]
-    L.ndq64_mlp_num_streams.argtypes = [dp]
-    L.ndq64_mlp_num_params.argtypes = [dp]
-    L.ndq64_mlp_bwd_blocks.argtypes = [dp, ci]
-    L.ndq64_mlp_jet_fwd.argtypes = [dp, vp, ci, ci, vp, vp, ci, vp]
-    L.ndq64_mlp_jet_bwd.argtypes = [dp, vp, ci, ci, vp, vp, ci, vp, vp]
-    L.ndq64_reduce_partials.argtypes = [vp, ci, ci, vp, ci, ctypes.c_double, vp]
-    L.ndq64_mlp_register.argtypes = [vp]
-    cd = ctypes.c_double
-    L.ndq64_adam_step.argtypes = [vp, vp, vp, vp, ci, cd, cd, cd, cd, cd, ci, vp]
-    L.ndq64_epoch_tail.argtypes = [vp, vp, vp, vp, ci, cd, cd, cd, cd, cd, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp]
-    L.ndq64_fused_step_bytes.argtypes = []
-    L.ndq64_reduce_tail.argtypes = [ctypes.POINTER(FusedStep64), ci, ci, ci, ci, vp]
-    L.ndq64_fused_step_run.argtypes = [ctypes.POINTER(FusedStep64), ci, vp, vp, ci, ci, ci, vp]
-    for name in EXPORTS64:
-        getattr(L, name).restype = ci
-    _LIB64 = L
-    return L
+    vp, ci = _vp, _ci
+    _LIB64 = _bind(ctypes.CDLL(_build.LIB64), "ndq64_", ctypes.c_double, {
+        "ndq64_fused_step_bytes": [],
+        "ndq64_reduce_tail": [ctypes.POINTER(FusedStep64), ci, ci, ci, ci, vp],
+        "ndq64_fused_step_run": [ctypes.POINTER(FusedStep64), ci, vp, vp, ci, ci, ci, vp],
+    }, EXPORTS64)
+    return _LIB64
 
 
 EXPORTS64 = ("ndq64_mlp_register", "ndq64_mlp_supported", "ndq64_mlp_num_streams", "ndq64_mlp_num_params",

@@ -1,7 +1,8 @@
-// C-ABI of libndq.so (declared in include/ndq.h): descriptor dispatch onto the templated gfx950 kernels of
-// ndq_mlp.h, the second-stage reduction and the fused Adam step.
+// C-ABI of libndq.so (declared in include/ndq.h).  Its own here: the built-in fp32 kernel table, the second-stage sums, the
+// sums + tail launches on every route (single GPU, data parallel, multi-network, fit()), the samplers and the one-shot
+// all-reduce.  Descriptor dispatch, epoch tail, Adam and the runner behind ndq_fused_multi_step_run are
+// csrc/ndq_api_common.h, shared with libndq64.so.
 #include <cstdlib>
-#include <vector>
 #include "ndq_launch.h"
 #include "ndq_sample.h"
 #include "ndq_oneshot.h"
@@ -65,18 +66,15 @@ namespace ndq {
 #endif
 
 #define NDQ_ENTRY(D, F, M, NB, L, A, O, LP) make_kernels<Cfg<D, F, M, NB, L, A, O, LP>>(),
+#define NDQ_API_KERNELS NDQ_CFG_TABLE(NDQ_ENTRY)
 
-static const ndq_mlp_kernels kTable[] = {NDQ_CFG_TABLE(NDQ_ENTRY)};
-static std::vector<const ndq_mlp_kernels*> g_registered;     // extension modules (ndq_mlp_register)
+static bool hidden_ok(const ndq_mlp_desc& d) { return d.hidden >= 1 && d.hidden <= NDQ_MAX_HIDDEN; }
 
-static const ndq_mlp_kernels* find(const ndq_mlp_desc* d) {
-  if (!d || d->hidden < 1 || d->hidden > NDQ_MAX_HIDDEN) return nullptr;
-  for (const ndq_mlp_kernels& e : kTable)
-    if (same_desc(e.desc, *d)) return &e;
-  for (const ndq_mlp_kernels* e : g_registered)
-    if (same_desc(e->desc, *d)) return e;
-  return nullptr;
-}
+}  // namespace ndq
+
+#include "ndq_api_common.h"
+
+namespace ndq {
 
 // ---------------------------------------------------------------------------------------------- reduction
 // out[i] = (acc ? out[i] : 0) + scale * sum_r partials[r*len + i];  one thread per 4 columns, rows in fixed order,
@@ -136,8 +134,7 @@ struct ColumnRows {
     float x[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) x[j] = v[j];
-    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]),
-                      "+v"(x[9]), "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15]));
+    NDQ_PIN16(x);
 #pragma unroll
     for (int j = 0; j < 16; ++j) x[j] = (rg + 16 * j < nparts && col < len) ? x[j] : 0.f;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -204,7 +201,7 @@ __global__ __launch_bounds__(1024) void reduce_grad_loss_kernel(Reduce2Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------- epoch tail
-// (epoch_tail_kernel, the tail of an epoch whose sums are done already -- ndq_epoch_tail -- lives in ndq_tail.h: it is shared with libndq64.so)
+// (the tail of an epoch whose sums are done already, ndq_epoch_tail: ndq_tail.h's kernel behind ndq_api_common.h's entry point)
 using TailArgs = ndq::TailArgsT<float>;
 
 // second-stage sums AND the epoch tail in one launch (single batch per epoch, no all-reduce in between): every
@@ -434,49 +431,6 @@ using namespace ndq;
 
 extern "C" {
 
-int ndq_mlp_supported(const ndq_mlp_desc* desc) { return find(desc) ? 1 : 0; }
-
-int ndq_mlp_register(const ndq_mlp_kernels* k) {
-  if (!k || !k->fwd || !k->bwd || k->desc.hidden < 1 || k->desc.hidden > NDQ_MAX_HIDDEN || k->n_streams < 1 || k->n_params < 1 || k->bwd_waves < 1 ||
-      k->lds_bytes > 160 * 1024)
-    return NDQ_EINVAL;
-  if (!find(&k->desc)) g_registered.push_back(k);
-  return 0;
-}
-
-int ndq_mlp_num_streams(const ndq_mlp_desc* desc) {
-  const ndq_mlp_kernels* e = find(desc);
-  return e ? e->n_streams : NDQ_EUNSUPPORTED;
-}
-
-int ndq_mlp_num_params(const ndq_mlp_desc* desc) {
-  const ndq_mlp_kernels* e = find(desc);
-  return e ? e->n_params : NDQ_EUNSUPPORTED;
-}
-
-int ndq_mlp_bwd_blocks(const ndq_mlp_desc* desc, int n) {
-  const ndq_mlp_kernels* e = find(desc);
-  if (!e) return NDQ_EUNSUPPORTED;
-  if (n <= 0) return NDQ_EINVAL;
-  return bwd_blocks(e->bwd_waves, n);
-}
-
-int ndq_mlp_jet_fwd(const ndq_mlp_desc* desc, const float* coords, int ldc, int n, const float* params, float* jets,
-                    int ldj, void* stream) {
-  const ndq_mlp_kernels* e = find(desc);
-  if (!e) return NDQ_EUNSUPPORTED;
-  if (!coords || !params || !jets || n <= 0 || ldc < n || ldj < n) return NDQ_EINVAL;
-  return e->fwd(coords, ldc, n, params, jets, ldj, stream);
-}
-
-int ndq_mlp_jet_bwd(const ndq_mlp_desc* desc, const float* coords, int ldc, int n, const float* params,
-                    const float* gbar, int ldj, float* partials, void* stream) {
-  const ndq_mlp_kernels* e = find(desc);
-  if (!e) return NDQ_EUNSUPPORTED;
-  if (!coords || !params || !gbar || !partials || n <= 0 || ldc < n || ldj < n) return NDQ_EINVAL;
-  return e->bwd(coords, ldc, n, params, gbar, ldj, partials, bwd_blocks(e->bwd_waves, n), stream);
-}
-
 int ndq_reduce_partials(const float* partials, int nparts, int len, float* out, int accumulate, float scale,
                         void* stream) {
   if (!partials || !out || nparts <= 0 || len <= 0) return NDQ_EINVAL;
@@ -490,23 +444,6 @@ int ndq_reduce_grad_loss(const float* partials, int nparts, int len, float* out,
   if (!partials || !out || !loss_partials || !loss_out || nparts <= 0 || len <= 0 || n_loss_parts <= 0) return NDQ_EINVAL;
   Reduce2Args a{partials, nparts, len, out, accumulate, loss_partials, n_loss_parts, loss_out, loss_scale};
   hipLaunchKernelGGL(reduce_grad_loss_kernel, dim3((len + 63) / 64 + 1), dim3(1024), 0, static_cast<hipStream_t>(stream), a);
-  return (int)hipGetLastError();
-}
-
-int ndq_epoch_tail(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int len, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int step, const float* loss_slots, int n_batches,
-                   float* loss_hist, int hist_index, float* best_loss, int parity, float* best_flat, int write_scalars,
-                   void* stream) {
-  const bool adam = exp_avg != nullptr;
-  if (!params || len <= 0 || !loss_slots || n_batches <= 0 || !loss_hist || !best_loss || hist_index < 0 ||
-      (parity != 0 && parity != 1) || (adam && (!grad || !exp_avg_sq || step <= 0)))
-    return NDQ_EINVAL;
-  TailArgs a{};
-  a.p = params; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.len = len;
-  a.adam = adam_consts(lr, beta1, beta2, eps, weight_decay, adam ? step : 0);
-  a.loss_slots = loss_slots; a.nb = n_batches; a.loss_hist = loss_hist; a.hist_index = hist_index;
-  a.best_loss = best_loss; a.parity = parity; a.best_flat = best_flat; a.write_scalars = write_scalars;
-  hipLaunchKernelGGL(epoch_tail_kernel<float>, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
 }
 
@@ -532,6 +469,19 @@ static ReduceTailArgs reduce_tail_args(const ndq_fused_step& s, const ndq_fused_
   a.tail_blocks = 0x7fffffff;
   a.v = v;
   return a;
+}
+
+// the sums + tail launch of validated steps: all networks behind one multi-network closure launch (fused_steps_run)
+static int reduce_tail_multi(const ndq_fused_step* steps, int n_nets, int adam_step, int hist_index, int parity, void* stream) {
+  const ndq_fused_step& s0 = steps[0];
+  ReduceTailMultiArgs a{};
+  int max_params = 0;
+  for (int k = 0; k < n_nets; ++k) {
+    a.net[k] = reduce_tail_args(steps[k], s0, steps[k].partials, s0.loss_partials, s0.blocks, adam_step, hist_index, parity,
+                                k == 0 ? 1 : 0, steps[k].best_flat);
+    if (steps[k].n_params > max_params) max_params = steps[k].n_params;
+  }
+  return launch_tail_multi(a, max_params, n_nets, s0.blocks, stream);
 }
 
 extern "C" {
@@ -584,30 +534,7 @@ int ndq_fused_step_run(const ndq_fused_step* s, const float* coords, int adam_st
 
 int ndq_fused_multi_step_run(const ndq_fused_step* steps, int n_nets, ndq_fused_launch_multi_fn launch,
                              const float* coords, int adam_step, int hist_index, int parity, void* stream) {
-  if (!steps || !launch || !coords || n_nets < 1 || n_nets > 4 || adam_step <= 0 || hist_index < 0 ||
-      (parity != 0 && parity != 1))
-    return NDQ_EINVAL;
-  const ndq_fused_step& s0 = steps[0];
-  if (!s0.loss_hist || !s0.best_loss || !s0.loss_partials) return NDQ_EINVAL;
-  const float* params[4];
-  float* partials[4];
-  for (int k = 0; k < n_nets; ++k) {
-    if (!steps[k].params || !steps[k].partials || !steps[k].grad || !steps[k].adam_m || !steps[k].adam_v ||
-        !steps[k].loss_slot)
-      return NDQ_EINVAL;
-    params[k] = steps[k].params;
-    partials[k] = steps[k].partials;
-  }
-  int rc = launch(coords, s0.ldc, s0.n, params, partials, s0.loss_partials, nullptr, nullptr, s0.ldj, s0.seed, 1, stream);
-  if (rc) return rc;
-  ReduceTailMultiArgs a{};
-  int max_params = 0;
-  for (int k = 0; k < n_nets; ++k) {
-    a.net[k] = reduce_tail_args(steps[k], s0, steps[k].partials, s0.loss_partials, s0.blocks, adam_step, hist_index, parity,
-                                k == 0 ? 1 : 0, steps[k].best_flat);
-    if (steps[k].n_params > max_params) max_params = steps[k].n_params;
-  }
-  return launch_tail_multi(a, max_params, n_nets, s0.blocks, stream);
+  return fused_steps_run(steps, n_nets, launch, coords, adam_step, hist_index, parity, stream, &reduce_tail_multi);
 }
 
 }  // extern "C"
@@ -808,14 +735,6 @@ int ndq_fused_fit_run(const ndq_fused_fit* f, int n_epochs, const float* const* 
     }
   }
   return loop ? fit_loop(c, stride, parity) : fit_pull(c, parity);
-}
-
-int ndq_adam_step(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int len, float lr, float beta1,
-                  float beta2, float eps, float weight_decay, int step, void* stream) {
-  if (!params || !grad || !exp_avg || !exp_avg_sq || len <= 0 || step <= 0) return NDQ_EINVAL;
-  hipLaunchKernelGGL(adam_kernel<float>, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), params, grad,
-                     exp_avg, exp_avg_sq, len, adam_consts(lr, beta1, beta2, eps, weight_decay, step));
-  return (int)hipGetLastError();
 }
 
 int ndq_sample(const ndq_sampler_desc* desc, unsigned long long seed, unsigned long long draw, unsigned stream_id,

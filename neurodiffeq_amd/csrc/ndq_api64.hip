@@ -1,9 +1,10 @@
-// libndq64.so: the stream kernels of ndq_mlp.h compiled for fp64 (NDQ_F64) behind the ndq64_* entry points of
-// include/ndq.h -- descriptor dispatch, forward streams, parameter-gradient adjoint, fixed-order second-stage sum.
-// Serves fp64 networks (the reference's default precision) through the torch custom ops of autograd_ops.py.
+// libndq64.so: the stream kernels of ndq_mlp.h compiled for fp64 (NDQ_F64) behind the ndq64_* entry points of include/ndq.h;
+// serves fp64 networks (the reference's default precision) through the torch custom ops of autograd_ops.py.  Its own here:
+// the built-in kernel table, the fixed-order second-stage sum in double and the fp64 sums + tail launch.  Descriptor dispatch,
+// epoch tail, Adam and the fused-step runner are csrc/ndq_api_common.h, shared with libndq.so.
 #define NDQ_F64 1
-#include <vector>
 #include "ndq_launch.h"
+#include "ndq_tail.h"
 
 namespace ndq {
 
@@ -18,20 +19,16 @@ namespace ndq {
   X(1, 1, 1, 2, 2, ACT_SIN, 1)
 
 #define NDQ64_ENTRY(D, F, M, NB, L, A, O) make_kernels<Cfg<D, F, M, NB, L, A, O, 0>>(),
-static const ndq64_mlp_kernels kTable64[] = {NDQ64_CFG_TABLE(NDQ64_ENTRY)};
-static std::vector<const ndq64_mlp_kernels*> g_registered64;
+#define NDQ_API_KERNELS NDQ64_CFG_TABLE(NDQ64_ENTRY)
 
 // (hidden > 64: ONE hidden layer of up to 512 units -- csrc/ndq_wide.h compiled in double, registered extension modules only)
-static bool hidden_ok64(const ndq_mlp_desc& d) { return d.hidden >= 1 && d.hidden <= (d.layers == 1 ? 512 : 64); }
+static bool hidden_ok(const ndq_mlp_desc& d) { return d.hidden >= 1 && d.hidden <= (d.layers == 1 ? 512 : 64); }
 
-static const ndq64_mlp_kernels* find64(const ndq_mlp_desc* d) {
-  if (!d || !hidden_ok64(*d)) return nullptr;
-  for (const ndq64_mlp_kernels& e : kTable64)
-    if (same_desc(e.desc, *d)) return &e;
-  for (const ndq64_mlp_kernels* e : g_registered64)
-    if (same_desc(e->desc, *d)) return e;
-  return nullptr;
-}
+}  // namespace ndq
+
+#include "ndq_api_common.h"
+
+namespace ndq {
 
 // out[i] = (acc ? out[i] : 0) + scale * sum_r partials[r*len + i], rows in fixed order.  A workgroup owns 64 columns; its
 // 16 row groups each add up every 16th row in four independent chains, the 16 group sums are added in index order (the
@@ -58,8 +55,7 @@ __global__ __launch_bounds__(1024) void reduce_partials64_kernel(const double* _
       const int r = base + rg + 16 * j;
       x[j] = part[(size_t)(r < nparts ? r : nparts - 1) * len + cc];
     }
-    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]),
-                      "+v"(x[9]), "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15]));
+    NDQ_PIN16(x);
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int r0 = base + rg + 64 * it;
@@ -145,10 +141,8 @@ __global__ __launch_bounds__(1024) void reduce_tail64_kernel(ReduceTail64Args a)
   double pi = 0., m0 = 0., v0 = 0.;
   if (upd) { pi = mine.t.p[i]; m0 = mine.t.m[i]; v0 = mine.t.v[i]; }
   double best = a.best_loss[a.parity];                      // (uniform address: a scalar load, pinned below like the rest)
-  asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]),
-                    "+v"(x[9]), "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15]));
-  asm volatile("" : "+v"(y[0]), "+v"(y[1]), "+v"(y[2]), "+v"(y[3]), "+v"(y[4]), "+v"(y[5]), "+v"(y[6]), "+v"(y[7]), "+v"(y[8]),
-                    "+v"(y[9]), "+v"(y[10]), "+v"(y[11]), "+v"(y[12]), "+v"(y[13]), "+v"(y[14]), "+v"(y[15]));
+  NDQ_PIN16(x);
+  NDQ_PIN16(y);
   asm volatile("" : "+s"(best));
   double s0 = 0., s1 = 0., s2 = 0., s3 = 0., l0 = 0., l1 = 0., l2 = 0., l3 = 0.;
   column_chunk64(x, 0, rg, nparts, s0, s1, s2, s3);
@@ -160,10 +154,8 @@ __global__ __launch_bounds__(1024) void reduce_tail64_kernel(ReduceTail64Args a)
       x[j] = mine.part[(size_t)rr * len + cc];
       y[j] = a.lpart[rr];
     }
-    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]),
-                      "+v"(x[9]), "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15]));
-    asm volatile("" : "+v"(y[0]), "+v"(y[1]), "+v"(y[2]), "+v"(y[3]), "+v"(y[4]), "+v"(y[5]), "+v"(y[6]), "+v"(y[7]), "+v"(y[8]),
-                      "+v"(y[9]), "+v"(y[10]), "+v"(y[11]), "+v"(y[12]), "+v"(y[13]), "+v"(y[14]), "+v"(y[15]));
+    NDQ_PIN16(x);
+    NDQ_PIN16(y);
     column_chunk64(x, base, rg, nparts, s0, s1, s2, s3);
     column_chunk64(y, base, rg, nparts, l0, l1, l2, l3);
   }
@@ -201,102 +193,8 @@ __global__ __launch_bounds__(1024) void reduce_tail64_kernel(ReduceTail64Args a)
 
 using namespace ndq;
 
-extern "C" {
-
-int ndq64_mlp_supported(const ndq_mlp_desc* desc) { return find64(desc) ? 1 : 0; }
-
-int ndq64_mlp_register(const ndq64_mlp_kernels* k) {
-  if (!k || !k->fwd || !k->bwd || !hidden_ok64(k->desc) || k->n_streams < 1 || k->n_params < 1 || k->bwd_waves < 1 ||
-      k->lds_bytes > 160 * 1024)
-    return NDQ_EINVAL;
-  if (!find64(&k->desc)) g_registered64.push_back(k);
-  return 0;
-}
-
-int ndq64_mlp_num_streams(const ndq_mlp_desc* desc) {
-  const ndq64_mlp_kernels* e = find64(desc);
-  return e ? e->n_streams : NDQ_EUNSUPPORTED;
-}
-
-int ndq64_mlp_num_params(const ndq_mlp_desc* desc) {
-  const ndq64_mlp_kernels* e = find64(desc);
-  return e ? e->n_params : NDQ_EUNSUPPORTED;
-}
-
-int ndq64_mlp_bwd_blocks(const ndq_mlp_desc* desc, int n) {
-  const ndq64_mlp_kernels* e = find64(desc);
-  if (!e) return NDQ_EUNSUPPORTED;
-  if (n <= 0) return NDQ_EINVAL;
-  return bwd_blocks(e->bwd_waves, n);
-}
-
-int ndq64_mlp_jet_fwd(const ndq_mlp_desc* desc, const double* coords, int ldc, int n, const double* params, double* jets,
-                      int ldj, void* stream) {
-  const ndq64_mlp_kernels* e = find64(desc);
-  if (!e) return NDQ_EUNSUPPORTED;
-  if (!coords || !params || !jets || n <= 0 || ldc < n || ldj < n) return NDQ_EINVAL;
-  return e->fwd(coords, ldc, n, params, jets, ldj, stream);
-}
-
-int ndq64_mlp_jet_bwd(const ndq_mlp_desc* desc, const double* coords, int ldc, int n, const double* params,
-                      const double* gbar, int ldj, double* partials, void* stream) {
-  const ndq64_mlp_kernels* e = find64(desc);
-  if (!e) return NDQ_EUNSUPPORTED;
-  if (!coords || !params || !gbar || !partials || n <= 0 || ldc < n || ldj < n) return NDQ_EINVAL;
-  return e->bwd(coords, ldc, n, params, gbar, ldj, partials, bwd_blocks(e->bwd_waves, n), stream);
-}
-
-int ndq64_reduce_partials(const double* partials, int nparts, int len, double* out, int accumulate, double scale,
-                          void* stream) {
-  if (!partials || !out || nparts <= 0 || len <= 0) return NDQ_EINVAL;
-  hipLaunchKernelGGL(reduce_partials64_kernel, dim3((len + 63) / 64), dim3(1024), 0, static_cast<hipStream_t>(stream),
-                     partials, nparts, len, out, accumulate, scale);
-  return (int)hipGetLastError();
-}
-
-// Adam and the device-side end of an fp64 epoch: ndq_tail.h's adam_kernel / epoch_tail_kernel instantiated for double -- the
-// source libndq.so runs in float, so an epoch through ndq64_epoch_tail and one through ndq64_adam_step agree bit for bit
-int ndq64_adam_step(double* params, const double* grad, double* exp_avg, double* exp_avg_sq, int len, double lr,
-                    double beta1, double beta2, double eps, double weight_decay, int step, void* stream) {
-  if (!params || !grad || !exp_avg || !exp_avg_sq || len <= 0 || step <= 0) return NDQ_EINVAL;
-  hipLaunchKernelGGL(adam_kernel<double>, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), params, grad,
-                     exp_avg, exp_avg_sq, len, adam_consts(lr, beta1, beta2, eps, weight_decay, step));
-  return (int)hipGetLastError();
-}
-
-int ndq64_epoch_tail(double* params, const double* grad, double* exp_avg, double* exp_avg_sq, int len, double lr,
-                     double beta1, double beta2, double eps, double weight_decay, int step, const double* loss_slots,
-                     int n_batches, double* loss_hist, int hist_index, double* best_loss, int parity, double* best_flat,
-                     int write_scalars, void* stream) {
-  const bool adam = exp_avg != nullptr;
-  if (!params || len <= 0 || !loss_slots || n_batches <= 0 || !loss_hist || !best_loss || hist_index < 0 ||
-      (parity != 0 && parity != 1) || (adam && (!grad || !exp_avg_sq || step <= 0)))
-    return NDQ_EINVAL;
-  TailArgsT<double> a{};
-  a.p = params; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.len = len;
-  a.adam = adam_consts(lr, beta1, beta2, eps, weight_decay, adam ? step : 0);
-  a.loss_slots = loss_slots; a.nb = n_batches; a.loss_hist = loss_hist; a.hist_index = hist_index;
-  a.best_loss = best_loss; a.parity = parity; a.best_flat = best_flat; a.write_scalars = write_scalars;
-  hipLaunchKernelGGL(epoch_tail_kernel<double>, dim3((len + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return (int)hipGetLastError();
-}
-
-int ndq64_fused_step_bytes(void) { return (int)sizeof(ndq64_fused_step); }
-
-// what both entry points below check before any HIP call
-static bool fused_steps_ok64(const ndq64_fused_step* steps, int n_nets, int adam_step, int hist_index, int parity) {
-  if (!steps || n_nets < 1 || n_nets > 4 || adam_step <= 0 || hist_index < 0 || (parity != 0 && parity != 1)) return false;
-  const ndq64_fused_step& s0 = steps[0];
-  if (!s0.loss_partials || !s0.loss_hist || !s0.best_loss || !s0.loss_slot || s0.blocks <= 0) return false;
-  for (int k = 0; k < n_nets; ++k) {
-    const ndq64_fused_step& s = steps[k];
-    if (!s.params || !s.partials || !s.grad || !s.adam_m || !s.adam_v || s.n_params <= 0) return false;
-  }
-  return true;
-}
-
-int ndq64_reduce_tail(const ndq64_fused_step* steps, int n_nets, int adam_step, int hist_index, int parity, void* stream) {
-  if (!fused_steps_ok64(steps, n_nets, adam_step, hist_index, parity)) return NDQ_EINVAL;
+// the sums + tail launch of validated steps
+static int reduce_tail64_launch(const ndq64_fused_step* steps, int n_nets, int adam_step, int hist_index, int parity, void* stream) {
   const ndq64_fused_step& s0 = steps[0];
   ReduceTail64Args a{};
   a.lpart = s0.loss_partials; a.nparts = s0.blocks; a.lscale = s0.seed;
@@ -317,19 +215,26 @@ int ndq64_reduce_tail(const ndq64_fused_step* steps, int n_nets, int adam_step, 
   return (int)hipGetLastError();
 }
 
+extern "C" {
+
+int ndq64_reduce_partials(const double* partials, int nparts, int len, double* out, int accumulate, double scale,
+                          void* stream) {
+  if (!partials || !out || nparts <= 0 || len <= 0) return NDQ_EINVAL;
+  hipLaunchKernelGGL(reduce_partials64_kernel, dim3((len + 63) / 64), dim3(1024), 0, static_cast<hipStream_t>(stream),
+                     partials, nparts, len, out, accumulate, scale);
+  return (int)hipGetLastError();
+}
+
+int ndq64_fused_step_bytes(void) { return (int)sizeof(ndq64_fused_step); }
+
+int ndq64_reduce_tail(const ndq64_fused_step* steps, int n_nets, int adam_step, int hist_index, int parity, void* stream) {
+  if (!fused_steps_ok(steps, n_nets, adam_step, hist_index, parity)) return NDQ_EINVAL;
+  return reduce_tail64_launch(steps, n_nets, adam_step, hist_index, parity, stream);
+}
+
 int ndq64_fused_step_run(const ndq64_fused_step* steps, int n_nets, ndq64_fused_launch_multi_fn launch, const double* coords,
                          int adam_step, int hist_index, int parity, void* stream) {
-  if (!launch || !coords || !fused_steps_ok64(steps, n_nets, adam_step, hist_index, parity)) return NDQ_EINVAL;
-  const ndq64_fused_step& s0 = steps[0];
-  const double* params[4];
-  double* partials[4];
-  for (int k = 0; k < n_nets; ++k) {
-    params[k] = steps[k].params;
-    partials[k] = steps[k].partials;
-  }
-  int rc = launch(coords, s0.ldc, s0.n, params, partials, s0.loss_partials, nullptr, nullptr, s0.ldj, s0.seed, 1, stream);
-  if (rc) return rc;
-  return ndq64_reduce_tail(steps, n_nets, adam_step, hist_index, parity, stream);
+  return fused_steps_run(steps, n_nets, launch, coords, adam_step, hist_index, parity, stream, &reduce_tail64_launch);
 }
 
 }  // extern "C"

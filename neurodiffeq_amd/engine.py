@@ -1121,46 +1121,19 @@ class FusedSystem:
             fs["pending_valid"] += 1
         fs["parity"] ^= 1
 
-    def fast_train_epoch_multi(self, batch, adam_slots, track_best):
-        """fast_train_epoch for 2..4 networks behind ONE closure launch: closure kernel, then one fused sums + tail
-        kernel per network, all from one native call (ndq_fused_multi_step_run)."""
+    def fast_train_epoch_nets(self, batch, adam_slots, track_best):
+        """A training epoch of all networks behind ONE closure launch from one native call: closure kernel, then one sums +
+        tail launch for all networks.  fp32 (2..4 networks, ``fast_ready``): ndq_fused_multi_step_run.  fp64 (1..4 networks,
+        ``f64_tail_ready``): ndq64_fused_step_run, which leaves, bit for bit, what step() + epoch_tail() leave -- the loss in
+        ``loss_buf[0]`` included.  The caller has checked that all networks are at one Adam step (slot 0's is used)."""
         fs = self.fast_state()
         b, n = self.upload(batch)
         K = len(self.flat)
-        key = (n, b["ld"], id(b), "multi")
+        step_type, run = (_lib.FusedStep64, "ndq64_fused_step_run") if self.f64 else (_lib.FusedStep, "ndq_fused_multi_step_run")
+        key = (n, b["ld"], id(b), "f64" if self.f64 else "multi")
         arr = fs["structs"].get(key)
         if arr is None:
-            arr = (_lib.FusedStep * K)()
-            for k in range(K):
-                self._fill_step(arr[k], k, n, b["ld"], b["fused_blocks"], b["fused_partials_all"][k], b["fused_loss_partials"])
-            fs["structs"][key] = arr
-        step = None
-        for k, fp in enumerate(self.flat):
-            fp.sync()
-            m, v, group, step_k = adam_slots[k]
-            step = step_k if step is None else step
-            st = arr[k]
-            st.params = fp.flat.data_ptr()
-            st.seed = 1.0 / (float(n) * self.loss_norm)
-            st.best_flat = fs["best_flat"][k].data_ptr() if track_best else None
-            self._set_adam(st, m, v, group)
-        rc = self.L.ndq_fused_multi_step_run(arr, K, _c_vp(b["fused_launch_multi"]), self._coord_ptr(b, 0), step,
-                                             fs["pending"], fs["parity"], self._stream())
-        _lib.check(rc, "ndq_fused_multi_step_run")
-        fs["pending"] += 1
-        fs["parity"] ^= 1
-
-    def fast_train_epoch_f64(self, batch, adam_slots, track_best):
-        """fast_train_epoch_multi in double, for 1..4 networks (``f64_tail_ready``): the closure kernel, then ONE sums + tail
-        kernel for all networks, from one native call (ndq64_fused_step_run).  Leaves, bit for bit, what step() + epoch_tail()
-        leave -- the loss in ``loss_buf[0]`` included."""
-        fs = self.fast_state()
-        b, n = self.upload(batch)
-        K = len(self.flat)
-        key = (n, b["ld"], id(b), "f64")
-        arr = fs["structs"].get(key)
-        if arr is None:
-            arr = (_lib.FusedStep64 * K)()
+            arr = (step_type * K)()
             for k in range(K):
                 self._fill_step(arr[k], k, n, b["ld"], b["fused_blocks"], b["fused_partials_all"][k], b["fused_loss_partials"])
             fs["structs"][key] = arr
@@ -1171,12 +1144,13 @@ class FusedSystem:
             st = arr[k]
             st.params = fp.flat.data_ptr()
             st.seed = 1.0 / (float(n) * self.loss_norm)
-            st.loss_slot = self.loss_buf.data_ptr()      # (where the parent's route keeps the epoch loss of batch 0)
+            if self.f64:
+                st.loss_slot = self.loss_buf.data_ptr()      # (where the step() + epoch_tail() route keeps the loss of batch 0)
             st.best_flat = fs["best_flat"][k].data_ptr() if track_best else None
             self._set_adam(st, m, v, group)
-        rc = self.L.ndq_fused_step_run(arr, K, _c_vp(b["fused_launch_multi"]), self._coord_ptr(b, 0), step, fs["pending"],
-                                       fs["parity"], self._stream())
-        _lib.check(rc, "ndq64_fused_step_run")
+        rc = getattr(self.L, run)(arr, K, _c_vp(b["fused_launch_multi"]), self._coord_ptr(b, 0), step, fs["pending"], fs["parity"],
+                                  self._stream())
+        _lib.check(rc, run)
         fs["pending"] += 1
         fs["parity"] ^= 1
 

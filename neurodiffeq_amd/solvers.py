@@ -743,7 +743,7 @@ class BaseSolver(ABC):
         # (fp64 systems -- the reference's default precision -- have no multi-epoch call: they run their per-batch launch
         # sequence (closure kernel in double, or the three-kernel pipeline) and then the device-side epoch tail in double,
         # ndq64_epoch_tail: 2 + 2 K launches behind a closure kernel.  Opt-in, NDQ_F64_FUSED_TAIL=1: a one-batch training
-        # epoch behind a closure kernel is ONE native call of two launches, engine.fast_train_epoch_f64 -- same bits)
+        # epoch behind a closure kernel is ONE native call of two launches, engine.fast_train_epoch_nets -- same bits)
         train = key == "train"
         nb = self.n_batches[key]
         track_best = (not train) or self.n_batches["valid"] == 0
@@ -776,10 +776,10 @@ class BaseSolver(ABC):
             pass        # one epoch through ndq_fused_fit_run: the device code the multi-epoch path of fit() runs
         elif train and nb == 1 and len(system.flat) > 1 and system.fast_ready(shard) and len({s[3] for s in slots}) == 1:
             # several networks behind one closure launch, all at the same Adam step (always, unless states were edited)
-            system.fast_train_epoch_multi(first_batch, slots, track_best)
+            system.fast_train_epoch_nets(first_batch, slots, track_best)
         elif train and nb == 1 and shard is None and system.f64_tail_ready() and len({s[3] for s in slots}) == 1:
             # fp64, opt-in (NDQ_F64_FUSED_TAIL=1): closure launch + ONE sums / tail launch in double for all networks
-            system.fast_train_epoch_f64(first_batch, slots, track_best)
+            system.fast_train_epoch_nets(first_batch, slots, track_best)
         elif train and nb == 1 and len(system.flat) == 1 and system.fast_ready(shard):
             batch = first_batch
             n_all = batch[0].shape[0]

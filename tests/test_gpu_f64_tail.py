@@ -1,5 +1,5 @@
 """The fp64 sums + tail launch (csrc/ndq_api64.hip: reduce_tail64_kernel) and the solver route through it
-(NDQ_F64_FUSED_TAIL=1: engine.fast_train_epoch_f64 -> ndq64_fused_step_run) on the GPU.
+(NDQ_F64_FUSED_TAIL=1: engine.fast_train_epoch_nets -> ndq64_fused_step_run) on the GPU.
 
 Everything here is held to EQUAL BITS against the route the switch replaces -- ndq64_reduce_partials per network, the loss sum
 (len = 1, scale = seed), ndq64_epoch_tail per network -- because summation orders are part of the contract (csrc/ndq_tail.h):
@@ -300,15 +300,15 @@ def test_three_epochs_on_the_new_route_follow_the_reference(golden_dir, monkeypa
 # ---------------------------------------------------------------------------------------------- routes that must not take it
 @pytest.fixture
 def native_calls(monkeypatch):
-    """Counts the epochs that went through engine.fast_train_epoch_f64."""
+    """Counts the epochs that went through engine.fast_train_epoch_nets."""
     from neurodiffeq_amd.engine import FusedSystem
     calls = []
-    inner = FusedSystem.fast_train_epoch_f64
+    inner = FusedSystem.fast_train_epoch_nets
 
     def counted(self, *args, **kw):
         calls.append(self)
         return inner(self, *args, **kw)
-    monkeypatch.setattr(FusedSystem, "fast_train_epoch_f64", counted)
+    monkeypatch.setattr(FusedSystem, "fast_train_epoch_nets", counted)
     return calls
 
 
