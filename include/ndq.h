@@ -393,8 +393,45 @@ typedef int (*ndq_pw_blocks_fn)(int n);
  * sum of per-point adjoints (block rows theta_partials [blocks][n_theta], second stage: ndq_reduce_partials), and
  * the n_data per-point columns are rows [d, d + n_data) of the coordinate block.  Every generated module (pointwise:
  * ndq_pw_bind_theta, closure: ndq_fused_bind_theta) exports the binder below; it is called before a launch whenever
- * n_theta > 0 (theta_partials may be NULL for forward-only launches). */
+ * n_theta > 0 (theta_partials may be NULL for forward-only launches).
+ * The END of such an epoch stays on the device as well when the optimiser is the package's FusedAdam and owns the scalars
+ * (ndq_theta_step below): the sums + tail launch of the epoch carries one more row that reduces theta_partials in
+ * ndq_reduce_partials' order and applies Adam to the scalars -- two launches per epoch, as for a forward problem. */
 typedef void (*ndq_bind_theta_fn)(const float* theta, float* theta_partials);
+
+/* The trainable scalars of an inverse problem for the sums + tail launch of a training epoch: one extra workgroup of that
+ * launch (an extra blockIdx.y row behind the networks') sums partials [blocks][n_theta] per column -- fp64 accumulators,
+ * four interleaved row chains combined as (s0 + s1) + (s2 + s3), i.e. bit for bit ndq_reduce_partials(partials, blocks,
+ * n_theta, gtheta, 0, 1) -- and then updates scalar j with ndq_adam_step's arithmetic under ITS OWN constants (scalars
+ * commonly sit in a parameter group of their own): lr[j] .. weight_decay[j] and the bias corrections of update number
+ * step[j].  Bit j of `frozen` set: scalar j is a runtime constant of the equations (no gradient step): its value and its
+ * moment slots are left untouched; gtheta[j] is still written.  `blocks` is ndq_fused_step.blocks of network 0. */
+#define NDQ_THETA_MAX 32
+typedef struct ndq_theta_step {
+  int n_theta;                /* 1..NDQ_THETA_MAX */
+  unsigned frozen;            /* bit j: scalar j takes no optimiser step */
+  float* theta;               /* [n_theta] the vector the closure launch reads (ndq_bind_theta_fn) */
+  const float* partials;      /* [blocks][n_theta] the block sums the closure launch writes */
+  float* gtheta;              /* [n_theta] reduced gradient (out) */
+  float* adam_m;              /* [n_theta] */
+  float* adam_v;              /* [n_theta] */
+  float lr[NDQ_THETA_MAX], beta1[NDQ_THETA_MAX], beta2[NDQ_THETA_MAX], eps[NDQ_THETA_MAX], weight_decay[NDQ_THETA_MAX];
+  int step[NDQ_THETA_MAX];    /* step count AFTER this update, per scalar (> 0 unless frozen) */
+} ndq_theta_step;
+/* sizeof(ndq_theta_step): lets a binding check its mirror of the struct without a GPU */
+int ndq_theta_step_bytes(void);
+/* Host only: the seven constants {lr, beta1, beta2, eps, weight_decay, 1 - beta1^t, sqrt(1 - beta2^t)} the launch applies to
+ * scalar j of `th` -- what ndq_adam_step computes from the same hyper-parameters and step count. */
+int ndq_theta_step_consts(const ndq_theta_step* th, int j, float* out7);
+/* ndq_fused_step_run (single GPU, no prefetch: allreduce / comm / next_* of `s` are ignored) and ndq_fused_multi_step_run
+ * with the scalars `th` riding in the sums + tail launch: closure launch, then ONE launch that finishes the epoch for the
+ * 1..4 networks and the scalars.  Networks, loss, history and best snapshot: bit for bit what the entry points without
+ * `th` leave.  The caller has bound th->theta / th->partials to the closure module. */
+int ndq_fused_theta_step_run(const ndq_fused_step* s, const ndq_theta_step* th, const float* coords, int adam_step,
+                             int hist_index, int parity, void* stream);
+int ndq_fused_theta_multi_step_run(const ndq_fused_step* steps, int n_nets, ndq_fused_launch_multi_fn launch,
+                                   const ndq_theta_step* th, const float* coords, int adam_step, int hist_index, int parity,
+                                   void* stream);
 
 /* ---- fp64 variants (libndq64.so) ------------------------------------------------------------------------------------
  * The reference's default precision is fp64 (neurodiffeq/__init__.py:22, utils.py:10-41).  libndq64.so carries the SAME

@@ -93,6 +93,18 @@ class FusedStep(ctypes.Structure):
                 ("next_stream", ctypes.c_uint), ("next_coords", ctypes.c_void_p), ("next_ldc", ctypes.c_int)]
 
 
+NDQ_THETA_MAX = 32
+
+
+class ThetaStep(ctypes.Structure):
+    """ndq_theta_step of include/ndq.h"""
+    _fields_ = [("n_theta", ctypes.c_int), ("frozen", ctypes.c_uint),
+                ("theta", ctypes.c_void_p), ("partials", ctypes.c_void_p), ("gtheta", ctypes.c_void_p),
+                ("adam_m", ctypes.c_void_p), ("adam_v", ctypes.c_void_p),
+                ("lr", ctypes.c_float * 32), ("beta1", ctypes.c_float * 32), ("beta2", ctypes.c_float * 32),
+                ("eps", ctypes.c_float * 32), ("weight_decay", ctypes.c_float * 32), ("step", ctypes.c_int * 32)]
+
+
 class FusedStep64(ctypes.Structure):
     """ndq64_fused_step of include/ndq.h"""
     _fields_ = [("n", ctypes.c_int), ("ldc", ctypes.c_int), ("ldj", ctypes.c_int), ("blocks", ctypes.c_int),
@@ -170,6 +182,10 @@ def lib():
         "ndq_fused_step_run": [ctypes.POINTER(FusedStep), vp, ci, ci, ci, vp],
         "ndq_fused_multi_step_run": [ctypes.POINTER(FusedStep), ci, vp, vp, ci, ci, ci, vp],
         "ndq_fused_fit_run": [ctypes.POINTER(FusedFit), ci, vp, ci, ci, ci, ci, vp],
+        "ndq_theta_step_bytes": [],
+        "ndq_theta_step_consts": [ctypes.POINTER(ThetaStep), ci, ctypes.POINTER(cf)],
+        "ndq_fused_theta_step_run": [ctypes.POINTER(FusedStep), ctypes.POINTER(ThetaStep), vp, ci, ci, ci, vp],
+        "ndq_fused_theta_multi_step_run": [ctypes.POINTER(FusedStep), ci, vp, ctypes.POINTER(ThetaStep), vp, ci, ci, ci, vp],
         "ndq_sample": [ctypes.POINTER(SamplerDesc), u64, u64, ctypes.c_uint, vp, ci, vp],
         "ndq_sample_table": [ctypes.POINTER(TableSamplerDesc), u64, u64, ctypes.c_uint, vp, ci, vp],
         "ndq_sample_plan": [ctypes.POINTER(PlanSamplerDesc), u64, u64, ctypes.c_uint, vp, ci, vp],
@@ -215,7 +231,8 @@ EXPORTS = ("ndq_mlp_supported", "ndq_mlp_num_streams", "ndq_mlp_num_params", "nd
            "ndq_mlp_jet_bwd", "ndq_reduce_partials", "ndq_adam_step", "ndq_reduce_grad_loss", "ndq_epoch_tail",
            "ndq_fused_step_run", "ndq_sample", "ndq_sample_table", "ndq_sample_plan", "ndq_sample_plan_indexed", "ndq_mlp_register",
            "ndq_fused_multi_step_run", "ndq_fused_fit_run", "ndq_oneshot_create", "ndq_oneshot_connect", "ndq_oneshot_allreduce", "ndq_oneshot_status",
-           "ndq_oneshot_destroy")
+           "ndq_oneshot_destroy", "ndq_theta_step_bytes", "ndq_theta_step_consts", "ndq_fused_theta_step_run",
+           "ndq_fused_theta_multi_step_run")
 
 
 def check(rc, what):

@@ -425,6 +425,104 @@ static int launch_tail_multi(ReduceTailMultiArgs& a, int max_params, int n_nets,
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------- trainable scalars
+// The scalars of an inverse problem (include/ndq.h: ndq_theta_step) as one more row of the multi-network sums + tail launch:
+// workgroup (0, n_nets) reduces theta_partials [nparts][nt] and steps the scalars; the other workgroups of that row leave at
+// once.  Per-scalar Adam constants travel as kernel arguments (host: adam_consts from every scalar's own step count).
+constexpr int kThetaMax = NDQ_THETA_MAX;
+constexpr int kThetaStage = 2048;       // floats of partial rows one workgroup stages in LDS (more: the sum reads global memory)
+struct ThetaArgs {
+  int nt, nparts; unsigned frozen;
+  const float* part; float* theta; float* gtheta; float* m; float* v;
+  float lr[kThetaMax], b1[kThetaMax], b2[kThetaMax], eps[kThetaMax], wd[kThetaMax], bc1[kThetaMax], bc2s[kThetaMax];
+};
+// TT threads.  Latency-bound like the rest of the launch (everything read here was written by the closure launch): the partial
+// rows are ONE contiguous block of nparts * nt floats, which all threads fetch side by side -- kThetaStage / TT straight-line
+// clamped loads each -- next to the value and the moments of the scalar a thread owns; only then the first add.  Thread j < nt
+// then adds column j out of LDS in the order of reduce_partials_kernel (fp64 accumulators, chains over rows r, r + 1, r + 2,
+// r + 3 (+ 4 k), (s0 + s1) + (s2 + s3), scale 1): the same additions, the same bits.  No atomics; nothing depends on the grid.
+template <int TT>
+__device__ __forceinline__ void theta_row(const ThetaArgs& a) {
+  constexpr int PER = kThetaStage / TT;
+  static_assert(PER >= 1 && PER * TT == kThetaStage, "the workgroup fills the staging block exactly");
+  __shared__ float st[kThetaStage];
+  const int tid = threadIdx.x, nt = a.nt, nparts = a.nparts, total = nt * nparts;
+  const bool staged = total <= kThetaStage;              // uniform
+  float x[PER];
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const int e = tid + q * TT;
+    x[q] = a.part[e < total ? e : total - 1];
+  }
+  const bool mine = tid < nt;
+  const int j = mine ? tid : 0;
+  const float p0 = a.theta[j], m0 = a.m[j], v0 = a.v[j];
+#pragma unroll
+  for (int q = 0; q < PER; ++q) st[tid + q * TT] = x[q];
+  __syncthreads();
+  if (!mine) return;
+  double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
+  int r = 0;
+  if (staged) {
+    for (; r + 3 < nparts; r += 4) {
+      s0 += (double)st[r * nt + j];
+      s1 += (double)st[(r + 1) * nt + j];
+      s2 += (double)st[(r + 2) * nt + j];
+      s3 += (double)st[(r + 3) * nt + j];
+    }
+    for (; r < nparts; ++r) s0 += (double)st[r * nt + j];
+  } else {
+#pragma unroll 4
+    for (; r + 3 < nparts; r += 4) {
+      s0 += (double)a.part[(size_t)r * nt + j];
+      s1 += (double)a.part[(size_t)(r + 1) * nt + j];
+      s2 += (double)a.part[(size_t)(r + 2) * nt + j];
+      s3 += (double)a.part[(size_t)(r + 3) * nt + j];
+    }
+    for (; r < nparts; ++r) s0 += (double)a.part[(size_t)r * nt + j];
+  }
+  const float g = (float)(((s0 + s1) + (s2 + s3)) * (double)1.0f);
+  a.gtheta[j] = g;
+  if ((a.frozen >> j) & 1u) return;
+  ndq::AdamConsts c{};
+#pragma unroll
+  for (int k = 0; k < kThetaMax; ++k)                    // static indices into the kernel arguments, selected per lane
+    if (k == j) c = ndq::AdamConsts{a.lr[k], a.b1[k], a.b2[k], a.eps[k], a.wd[k], a.bc1[k], a.bc2s[k]};
+  float pn, mi, vi;
+  ndq::adam_value(c, p0, g, m0, v0, pn, mi, vi);
+  a.m[j] = mi;
+  a.v[j] = vi;
+  a.theta[j] = pn;
+}
+struct ReduceTailThetaArgs {
+  ReduceTailMultiArgs nets;
+  ThetaArgs th;
+  int n_nets;
+};
+static_assert(sizeof(ReduceTailThetaArgs) <= 4096, "kernel arguments of the sums + tail launch with scalars");
+template <int TC>
+__global__ __launch_bounds__(TC * 16) void reduce_tail_theta_kernel(ReduceTailThetaArgs a) {
+  if ((int)blockIdx.y == a.n_nets) {
+    if (blockIdx.x == 0) theta_row<TC * 16>(a.th);
+    return;
+  }
+  const ReduceTailArgs& mine = a.nets.net[blockIdx.y];
+  if ((int)blockIdx.x * TC >= mine.r.len) return;
+  reduce_tail_body<TC>(mine);
+}
+// launch_tail_multi with the scalars' row behind the networks' (the same workgroup shape for the same sizes)
+static int launch_tail_theta(ReduceTailThetaArgs& a, int max_params, int n_nets, int max_lparts, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  for (int k = n_nets; k < 4; ++k) a.nets.net[k] = a.nets.net[0];
+  a.n_nets = n_nets;
+  if (NDQ_TAIL_COLS < 64 && max_lparts <= NDQ_TAIL_COLS * 16)
+    hipLaunchKernelGGL(reduce_tail_theta_kernel<NDQ_TAIL_COLS>, dim3((max_params + NDQ_TAIL_COLS - 1) / NDQ_TAIL_COLS, n_nets + 1),
+                       dim3(NDQ_TAIL_COLS * 16), 0, st, a);
+  else
+    hipLaunchKernelGGL(reduce_tail_theta_kernel<64>, dim3((max_params + 63) / 64, n_nets + 1), dim3(1024), 0, st, a);
+  return (int)hipGetLastError();
+}
+
 }  // namespace ndq
 
 using namespace ndq;
@@ -535,6 +633,77 @@ int ndq_fused_step_run(const ndq_fused_step* s, const float* coords, int adam_st
 int ndq_fused_multi_step_run(const ndq_fused_step* steps, int n_nets, ndq_fused_launch_multi_fn launch,
                              const float* coords, int adam_step, int hist_index, int parity, void* stream) {
   return fused_steps_run(steps, n_nets, launch, coords, adam_step, hist_index, parity, stream, &reduce_tail_multi);
+}
+
+}  // extern "C"
+
+// ---- the same epoch with the scalars of an inverse problem in the sums + tail launch (ndq_theta_step)
+static bool theta_step_ok(const ndq_theta_step* th) {
+  if (!th || th->n_theta < 1 || th->n_theta > NDQ_THETA_MAX || !th->theta || !th->partials || !th->gtheta || !th->adam_m ||
+      !th->adam_v)
+    return false;
+  for (int j = 0; j < th->n_theta; ++j)
+    if (!((th->frozen >> j) & 1u) && th->step[j] <= 0) return false;
+  return true;
+}
+static ndq::AdamConsts theta_consts(const ndq_theta_step& th, int j) {
+  return adam_consts(th.lr[j], th.beta1[j], th.beta2[j], th.eps[j], th.weight_decay[j], th.step[j]);
+}
+// validated steps + scalars -> ONE launch (reduce_tail_theta_kernel: blockIdx.y = network, last row = the scalars)
+static int reduce_tail_theta(const ndq_fused_step* steps, int n_nets, const ndq_theta_step& th, int adam_step, int hist_index,
+                             int parity, void* stream) {
+  const ndq_fused_step& s0 = steps[0];
+  ReduceTailThetaArgs a{};
+  int max_params = 0;
+  for (int k = 0; k < n_nets; ++k) {
+    a.nets.net[k] = reduce_tail_args(steps[k], s0, steps[k].partials, s0.loss_partials, s0.blocks, adam_step, hist_index, parity,
+                                     k == 0 ? 1 : 0, steps[k].best_flat);
+    if (steps[k].n_params > max_params) max_params = steps[k].n_params;
+  }
+  ThetaArgs& t = a.th;
+  t.nt = th.n_theta; t.nparts = s0.blocks; t.frozen = th.frozen;
+  t.part = th.partials; t.theta = th.theta; t.gtheta = th.gtheta; t.m = th.adam_m; t.v = th.adam_v;
+  for (int j = 0; j < th.n_theta; ++j) {
+    const ndq::AdamConsts c = theta_consts(th, j);
+    t.lr[j] = c.lr; t.b1[j] = c.b1; t.b2[j] = c.b2; t.eps[j] = c.eps; t.wd[j] = c.wd; t.bc1[j] = c.bc1; t.bc2s[j] = c.bc2s;
+  }
+  return launch_tail_theta(a, max_params, n_nets, s0.blocks, stream);
+}
+
+extern "C" {
+
+int ndq_theta_step_bytes(void) { return (int)sizeof(ndq_theta_step); }
+
+int ndq_theta_step_consts(const ndq_theta_step* th, int j, float* out7) {
+  if (!th || !out7 || j < 0 || j >= th->n_theta || th->n_theta > NDQ_THETA_MAX) return NDQ_EINVAL;
+  const ndq::AdamConsts c = theta_consts(*th, j);
+  out7[0] = c.lr; out7[1] = c.b1; out7[2] = c.b2; out7[3] = c.eps; out7[4] = c.wd; out7[5] = c.bc1; out7[6] = c.bc2s;
+  return 0;
+}
+
+int ndq_fused_theta_step_run(const ndq_fused_step* s, const ndq_theta_step* th, const float* coords, int adam_step,
+                             int hist_index, int parity, void* stream) {
+  if (!s || !s->launch || !coords || !theta_step_ok(th) || !fused_steps_ok(s, 1, adam_step, hist_index, parity)) return NDQ_EINVAL;
+  int rc = s->launch(coords, s->ldc, s->n, s->params, s->partials, s->loss_partials, nullptr, nullptr, s->ldj, s->seed, 1,
+                     stream);
+  if (rc) return rc;
+  return reduce_tail_theta(s, 1, *th, adam_step, hist_index, parity, stream);
+}
+
+int ndq_fused_theta_multi_step_run(const ndq_fused_step* steps, int n_nets, ndq_fused_launch_multi_fn launch,
+                                   const ndq_theta_step* th, const float* coords, int adam_step, int hist_index, int parity,
+                                   void* stream) {
+  if (!launch || !coords || !theta_step_ok(th) || !fused_steps_ok(steps, n_nets, adam_step, hist_index, parity)) return NDQ_EINVAL;
+  const ndq_fused_step& s0 = steps[0];
+  const float* params[4];
+  float* partials[4];
+  for (int k = 0; k < n_nets; ++k) {
+    params[k] = steps[k].params;
+    partials[k] = steps[k].partials;
+  }
+  int rc = launch(coords, s0.ldc, s0.n, params, partials, s0.loss_partials, nullptr, nullptr, s0.ldj, s0.seed, 1, stream);
+  if (rc) return rc;
+  return reduce_tail_theta(steps, n_nets, *th, adam_step, hist_index, parity, stream);
 }
 
 }  // extern "C"

@@ -361,6 +361,35 @@ def f64_fused_tail_switch(environ=None):
     return environ.get("NDQ_F64_FUSED_TAIL", "0") == "1"
 
 
+def theta_tail_switch(environ=None):
+    """On by default; NDQ_NO_THETA_TAIL=1 keeps inverse problems on the general epoch path (host-side optimiser step for the
+    scalars).  A pure function of the mapping it is given (default: the process environment)."""
+    environ = os.environ if environ is None else environ
+    return environ.get("NDQ_NO_THETA_TAIL", "0") != "1"
+
+
+def theta_tail_eligible(*, enabled, f64, closure, sharded, device, scalars, n_theta, optimizer):
+    """May the sums + tail launch of a training epoch step the trainable scalars of the equations (include/ndq.h:
+    ndq_theta_step)?  A pure function of what it is given: ``enabled`` (``theta_tail_switch``), fp32, a closure
+    kernel, no data-parallel shard, at least one trainable scalar and no more than the launch carries, every one of them a
+    WHOLE one-element float32 ``nn.Parameter`` on ``device`` (not entry k of a larger tensor) that ``optimizer`` -- a
+    FusedAdam -- owns in a group without amsgrad / maximize."""
+    from .optim import FusedAdam
+    if not enabled or f64 or not closure or sharded or not scalars or n_theta > _lib.NDQ_THETA_MAX:
+        return False
+    if not isinstance(optimizer, FusedAdam):
+        return False
+    device = torch.device(device)
+    for p in scalars:
+        if isinstance(p, tuple) or not isinstance(p, torch.nn.Parameter) or p.numel() != 1:
+            return False
+        # ("cuda" without an index names the current device: only two explicit indices can differ)
+        same = p.device.type == device.type and (p.device.index is None or device.index is None or p.device.index == device.index)
+        if not same or p.dtype != torch.float32 or not optimizer.owns_scalar(p):
+            return False
+    return True
+
+
 class FusedSystem:
     def __init__(self, nets, conditions, diff_eqs, n_coords, device, compute_func_val=None, single_kernel=True,
                  loss="l2", metrics=(), dtype=torch.float32, volatile=frozenset()):
@@ -383,6 +412,8 @@ class FusedSystem:
         self.esize = 8 if self.f64 else 4
         self.L = _Lib64() if self.f64 else _lib.lib()
         self.f64_fused_tail = self.f64 and f64_fused_tail_switch()      # read once, here (f64_tail_ready)
+        self.theta_tail = theta_tail_switch()                           # likewise (theta_tail_ready)
+        self._theta_owned = False         # True: theta_buf is authoritative for the trainable scalars (own_theta)
         self.nets, self.conditions, self.n_coords = list(nets), list(conditions), n_coords
         self.program, self.descs = trace_system(self.nets, self.conditions, diff_eqs, n_coords, compute_func_val, loss,
                                                 metrics, f64=self.f64, volatile=volatile)
@@ -468,10 +499,12 @@ class FusedSystem:
                 def value(p):      # a 1-element tensor, or entry k of a tensor (symbolic.Graph.param_elem)
                     v = p[0].detach().reshape(-1)[p[1]] if isinstance(p, tuple) else p.detach().reshape(())
                     return v.to(self.device, self.dt)
+                owned = self._theta_owned and self._theta_views_intact()
                 if not self.theta_frozen:
-                    self.theta_buf.copy_(torch.stack([value(p) for p in self.theta_params]))
+                    if not owned:
+                        self.theta_buf.copy_(torch.stack([value(p) for p in self.theta_params]))
                     return
-                if self._theta_trainable:
+                if self._theta_trainable and not owned:
                     live = torch.stack([value(self.theta_params[j]) for j in self._theta_trainable])
                     self.theta_buf[self._theta_trainable] = live
                 values = tuple(float(self.theta_params[j]) for j in self.theta_frozen)
@@ -508,6 +541,94 @@ class FusedSystem:
                 p.grad.copy_(g)
             else:
                 p.grad = g.clone()       # never a view of the shared buffer: the next epoch rewrites gtheta in place
+
+    # ---- the device owns the trainable scalars (the sums + tail launch steps them: fast_train_epoch_theta)
+    def theta_tail_ready(self, optimizer, dist=None):
+        """Can a one-batch training epoch of this inverse problem end on the device -- closure launch + ONE sums / tail launch
+        that also reduces and steps the trainable scalars (``theta_tail_eligible``; NDQ_NO_THETA_TAIL=1 when the system was
+        built: never)?  ``fast_ready()`` / ``fit_ready()`` keep their meaning."""
+        return theta_tail_eligible(enabled=self.theta_tail, f64=self.f64, closure=self.fusedk is not None,
+                                   sharded=dist is not None, device=self.device,
+                                   scalars=[self.theta_params[j] for j in self._theta_trainable], n_theta=self.n_theta,
+                                   optimizer=optimizer)
+
+    def _theta_views_intact(self):
+        base = self.theta_buf.data_ptr()
+        return all(self.theta_params[j].data_ptr() == base + 4 * j for j in self._theta_trainable)
+
+    def own_theta(self):
+        """``theta_buf`` becomes authoritative: every trainable scalar's ``.data`` is a view of its element (as FlatParams does
+        for network parameters), so an in-place edit by the user is what the next launch reads and what the tail writes is
+        what ``k.item()`` shows; ``k.grad`` is a VIEW of ``gtheta[j]`` -- like the ``.grad`` views of network parameters it is
+        rewritten in place by the next epoch (same stream, so never mid-read); a user who keeps a gradient clones it.
+        Frozen entries keep refresh_theta's mechanism."""
+        if not (self._theta_owned and self._theta_views_intact()):
+            with torch.no_grad():
+                for j in self._theta_trainable:
+                    p = self.theta_params[j]
+                    if p.data_ptr() != self.theta_buf.data_ptr() + 4 * j:
+                        self.theta_buf[j:j + 1].copy_(p.detach().reshape(1))
+                        p.data = self.theta_buf[j:j + 1].view(p.shape)
+            self._theta_owned = True
+        for j in self._theta_trainable:
+            p = self.theta_params[j]
+            if p.grad is None or p.grad.data_ptr() != self.gtheta.data_ptr() + 4 * j:
+                p.grad = self.gtheta[j:j + 1].view(p.shape)
+
+    def disown_theta(self):
+        """Back to the general path (another optimiser, ...): the host-side values are authoritative again.  The views stay
+        (a copy of a value onto itself is harmless); gradients become tensors of their own at the next attach_theta_grads."""
+        self._theta_owned = False
+
+    def fast_train_epoch_theta(self, batch, optimizer, adam_slots, track_best):
+        """A one-batch training epoch of an inverse problem from ONE native call of two launches and no host synchronisation:
+        closure kernel, then the sums + tail launch of all networks with the scalars as its last row
+        (ndq_fused_theta_step_run for one network, ndq_fused_theta_multi_step_run for 2..4).  The caller has checked
+        ``theta_tail_ready`` and that all networks are at one Adam step."""
+        fs = self.fast_state()
+        b, n = self.upload(batch)
+        self.set_batch_size(n)
+        self.own_theta()
+        self.refresh_theta()                         # (frozen runtime constants only)
+        K = len(self.flat)
+        key = (n, b["ld"], id(b), "theta")
+        ent = fs["structs"].get(key)
+        if ent is None:
+            arr = (_lib.FusedStep * K)()
+            for k in range(K):
+                self._fill_step(arr[k], k, n, b["ld"], b["fused_blocks"], b["fused_partials_all"][k], b["fused_loss_partials"])
+            arr[0].launch = b["fused_launch"]
+            th = _lib.ThetaStep()
+            th.n_theta, th.frozen = self.n_theta, sum(1 << j for j in self.theta_frozen)
+            th.theta, th.partials, th.gtheta = self.theta_buf.data_ptr(), b["theta_partials"].data_ptr(), self.gtheta.data_ptr()
+            ent = fs["structs"][key] = (arr, th)
+        arr, th = ent
+        if not optimizer.scalars_bound(self):
+            optimizer.bind_scalars(self, {j: self.theta_params[j] for j in self._theta_trainable}, self.n_theta, self.device)
+        tm, tv, per_scalar = optimizer.theta_slot()
+        th.adam_m, th.adam_v = tm.data_ptr(), tv.data_ptr()
+        for j, group, tstep in per_scalar:
+            th.lr[j], (th.beta1[j], th.beta2[j]), th.eps[j] = group["lr"], group["betas"], group["eps"]
+            th.weight_decay[j], th.step[j] = group["weight_decay"], tstep
+        step = adam_slots[0][3]
+        for k, fp in enumerate(self.flat):
+            fp.sync()
+            m, v, group, _ = adam_slots[k]
+            st = arr[k]
+            st.params = fp.flat.data_ptr()
+            st.seed = 1.0 / (float(n) * self.loss_norm)
+            st.best_flat = fs["best_flat"][k].data_ptr() if track_best else None
+            self._set_adam(st, m, v, group)
+        self._bind_theta(b, b["fusedk"].lib, True)
+        coords, stream = self._coord_ptr(b, 0), self._stream()
+        if K == 1:
+            rc = self.L.ndq_fused_theta_step_run(arr, ctypes.byref(th), coords, step, fs["pending"], fs["parity"], stream)
+        else:
+            rc = self.L.ndq_fused_theta_multi_step_run(arr, K, _c_vp(b["fused_launch_multi"]), ctypes.byref(th), coords, step,
+                                                       fs["pending"], fs["parity"], stream)
+        _lib.check(rc, "ndq_fused_theta_step_run")
+        fs["pending"] += 1
+        fs["parity"] ^= 1
 
     # ------------------------------------------------------------------------------------------ buffers
     def _resident_ld(self, batch):
@@ -1028,7 +1149,8 @@ class FusedSystem:
 
     def fast_ready(self, dist=None):
         """Can a whole training epoch go through one native call?  (single-launch closure; the data-parallel hook exists
-        for one network only)"""
+        for one network only).  Systems with scalar arguments of the equations (``n_theta``) are not served by THESE calls:
+        with trainable ones owned by a FusedAdam the epoch goes through ``fast_train_epoch_theta`` (``theta_tail_ready``)."""
         return self.fusedk is not None and (len(self.nets) == 1 or dist is None) and not self.f64 and not self.n_theta
 
     def f64_tail_ready(self):

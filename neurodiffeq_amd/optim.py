@@ -19,6 +19,7 @@ class FusedAdam(torch.optim.Adam):
         self._bound_ids = set()
         self._steps = {}
         self._dirty_steps = False
+        self._theta = None          # scalars of an inverse problem bound to a system's flat [NT] buffers (bind_scalars)
 
     # pickling / deepcopy (checkpoints: callbacks.py:129-155, solvers_utils.py:281-398): torch serialises defaults,
     # state and param_groups only, so the per-parameter ``step`` tensors are brought up to date first and the
@@ -31,12 +32,14 @@ class FusedAdam(torch.optim.Adam):
     def __setstate__(self, state):
         super().__setstate__(state)
         self._bound, self._bound_ids, self._steps, self._dirty_steps = [], set(), {}, False
+        self._theta = None
 
     def load_state_dict(self, state_dict):
         """Loaded moments / step counts live in fresh tensors: drop the binding, the solver binds again before its next
         native epoch and ``bind`` adopts them."""
         super().load_state_dict(state_dict)
         self._bound, self._bound_ids, self._steps, self._dirty_steps = [], set(), {}, False
+        self._theta = None
 
     def bind(self, flat_params):
         """Adopt the flat buffers of ``flat_params`` (list of FlatParams) for every parameter this optimiser owns."""
@@ -93,11 +96,65 @@ class FusedAdam(torch.optim.Adam):
                 return m, v, group, first
         return None
 
+    # ---- trainable scalars of the equations (inverse problems): the same arrangement as bind() for FlatParams.  The system
+    # keeps its NT scalars in one device vector; their moments become views of two flat [NT] buffers, so the sums + tail launch of
+    # an epoch can step them (include/ndq.h: ndq_theta_step).  Step counts are per scalar and tracked lazily.
+    def owns_scalar(self, p):
+        """Is ``p`` in a parameter group of this optimiser that the device-side update can serve (no amsgrad / maximize)?"""
+        for g in self.param_groups:
+            if any(q is p for q in g["params"]):
+                return not g.get("amsgrad") and not g.get("maximize")
+        return False
+
+    def bind_scalars(self, owner, scalars, n_theta, device):
+        """``scalars``: {index in the system's vector: one-element Parameter} -- the trainable ones, all owned by this optimiser
+        (``owns_scalar``).  Existing moments / step counts are adopted; entries of the [n_theta] buffers that belong to frozen
+        arguments stay zero and are never written.  ``owner``: the object whose vector this is (a re-bind to the same one is free)."""
+        th = self._theta
+        if th is not None and th["owner"] is owner and all(self.state[p].get("exp_avg") is v for p, v in zip(th["params"], th["mviews"])):
+            return
+        self._sync_step_tensors()
+        m = torch.zeros(n_theta, dtype=torch.float32, device=device)
+        v = torch.zeros(n_theta, dtype=torch.float32, device=device)
+        idx, params, steps, mviews = [], [], [], []
+        for j, p in sorted(scalars.items()):
+            st = self.state[p]
+            mv, vv = m[j:j + 1].view(p.shape), v[j:j + 1].view(p.shape)
+            if "exp_avg" in st:
+                mv.copy_(st["exp_avg"]); vv.copy_(st["exp_avg_sq"])
+                steps.append(int(st["step"]))
+            else:
+                steps.append(0)
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+            st["exp_avg"], st["exp_avg_sq"] = mv, vv
+            idx.append(j); params.append(p); mviews.append(mv)
+        self._theta = dict(owner=owner, m=m, v=v, idx=idx, params=params, steps=steps, mviews=mviews)
+
+    def scalars_bound(self, owner):
+        th = self._theta
+        return th is not None and th["owner"] is owner
+
+    def theta_slot(self):
+        """(exp_avg [NT], exp_avg_sq [NT], [(index, group, step AFTER the next update)] per bound scalar) for the native epoch,
+        which updates the scalars on the device; the counters advance.  Hyper-parameters: the scalar's own group, read now."""
+        th = self._theta
+        group_of = {id(p): g for g in self.param_groups for p in g["params"]}
+        out = []
+        for i, (j, p) in enumerate(zip(th["idx"], th["params"])):
+            th["steps"][i] += 1
+            out.append((j, group_of[id(p)], th["steps"][i]))
+        self._dirty_steps = True
+        return th["m"], th["v"], out
+
     def _sync_step_tensors(self):
         if getattr(self, "_dirty_steps", False):
             for fp, _, _, _ in self._bound:
                 for p in fp.params:
                     self.state[p]["step"].fill_(float(self._steps[id(fp)]))
+            th = getattr(self, "_theta", None)
+            if th is not None:
+                for p, step in zip(th["params"], th["steps"]):
+                    self.state[p]["step"].fill_(float(step))
             self._dirty_steps = False
 
     def state_dict(self):
@@ -137,4 +194,7 @@ class FusedAdam(torch.optim.Adam):
             finally:
                 for g, ps in zip(self.param_groups, saved):
                     g["params"] = ps
+            th = self._theta
+            if th is not None:           # bound scalars stepped by the stock implementation: follow its step counts
+                th["steps"] = [int(self.state[p]["step"]) if "step" in self.state[p] else s for p, s in zip(th["params"], th["steps"])]
         return loss

@@ -734,9 +734,22 @@ class BaseSolver(ABC):
         """Whole epoch with no host synchronisation.  Single-network systems with one batch per training epoch go
         through ONE native call (engine.fast_train_epoch: closure kernel + fused sums/tail kernel); every other fused
         system runs its per-batch launch sequence and then the device-side epoch tail (loss history ring, best
-        snapshot, fused Adam per network).  Returns False if the general (host-synchronising) path must run."""
-        if not self._native_ok() or system._theta_trainable:
-            return False        # (trainable equation coefficients are stepped by the user's optimiser: general path)
+        snapshot, fused Adam per network).  Inverse problems -- trainable scalars inside the equations -- whose FusedAdam owns
+        the scalars (engine.theta_tail_eligible) and that train on one batch per epoch stay here too: the training epoch is ONE
+        native call of two launches whose sums + tail launch also reduces and steps the scalars
+        (engine.fast_train_epoch_theta), validation epochs the per-batch sequence + epoch_tail.  Returns False if the general
+        (host-synchronising) path must run."""
+        if not self._native_ok():
+            return False
+        theta_route = False
+        if system._theta_trainable:
+            # trainable equation coefficients: on the device when the optimiser is a FusedAdam that owns every one of them
+            # (NDQ_NO_THETA_TAIL=1: never), else stepped by the user's optimiser on the general path.  Decided per system, for
+            # training and validation epochs alike, so that one history never mixes the two kinds of bookkeeping
+            theta_route = self.n_batches["train"] == 1 and system.theta_tail_ready(self.optimizer, self.dist)
+            if not theta_route:
+                system.disown_theta()
+                return False
         # (FROZEN scalar arguments -- runtime constants of a ramped coefficient, the batch size in the arithmetic: symbolic.Graph
         # .external / .nbatch -- need no optimiser: such systems keep the device-side epoch; step() refreshes the arguments.
         # fast_ready() / fit_ready() stay False for them, so they take the per-batch launch sequence + epoch_tail below)
@@ -756,6 +769,19 @@ class BaseSolver(ABC):
                 ok = system.verify_on(first_batch, self.dist.global_n(n_all) if self.dist else n_all, lo, hi)
                 if self.dist and not self.dist.agree(ok, self.device) and ok:
                     system.reject_fused()                 # ranks must take the same path: another rank rejected its kernel
+        if theta_route:
+            if system.fusedk is None:             # the closure kernel was rejected just now: no device-side scalar update
+                system.disown_theta()
+                return False
+            if train:
+                # (before any step counter advances: the one launch takes ONE Adam step count for all networks)
+                if not all(self.optimizer.bound(fp) for fp in system.flat):
+                    self.optimizer.bind(system.flat)
+                if not all(self.optimizer.bound(fp) for fp in system.flat) or \
+                        len({self.optimizer._steps.get(id(fp)) for fp in system.flat}) != 1:
+                    system.disown_theta()
+                    return False
+            system.own_theta()
         fs = system.fast_state()
         if max(fs["pending"], fs["pending_valid"]) >= system.HIST:
             self._flush_device_history()
@@ -772,7 +798,10 @@ class BaseSolver(ABC):
         shard = self.dist
         # (a static validation set served nb times -- the default: 4 x the same grid -- is nb identical losses: one batch)
         one_batch = nb == 1 or (not train and draws_are_static(self.generator["valid"]))
-        if shard is None and one_batch and system.fit_ready() and self._fit_epoch(key, system, first_batch, slots):
+        if theta_route and train:
+            # inverse problem: closure launch + ONE sums / tail launch that also steps the scalars of the equations
+            system.fast_train_epoch_theta(first_batch, self.optimizer, slots, track_best)
+        elif shard is None and one_batch and system.fit_ready() and self._fit_epoch(key, system, first_batch, slots):
             pass        # one epoch through ndq_fused_fit_run: the device code the multi-epoch path of fit() runs
         elif train and nb == 1 and len(system.flat) > 1 and system.fast_ready(shard) and len({s[3] for s in slots}) == 1:
             # several networks behind one closure launch, all at the same Adam step (always, unless states were edited)
