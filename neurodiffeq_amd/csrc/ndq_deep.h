@@ -23,23 +23,13 @@
 // products, fp32-class accuracy: csrc/ndq_mlp.h), the layer's weight planes resident in LDS for the whole launch; at W = 128
 // they are bound by the instructions they issue (jets, operand splits, products: profiles/r05b_deep_ab.md).  The weight-gradient
 // GEMM contracts over (point, stream) PAIRS, since round 5 on the same bf16x3 products (deep_wgrad_bf: a lane's 8 slots of a
-// chunk are the next 8 pair values it produces, no transposes); deep_wgrad_gemm (exact-f32 v_mfma_f32_16x16x4_f32, 4 points
-// per product) and deep_fwd_gemm / deep_bwd_gemm (exact-f32 per-point GEMMs) are kept behind -DNDQ_DEEP_WGRAD_BF=0 /
-// -DNDQ_DEEP_BF16X3=0 as the A/B baselines.
+// chunk are the next 8 pair values it produces, no transposes).  Measured against the exact-f32 kernels of rounds 4 - 5a
+// (v_mfma_f32_16x16x4_f32: per-point GEMMs and weight gradients), the plain blockIdx and a deep_head_bwd pass at every width:
+// profiles/r05b_deep_ab.md, DESIGN.md.
 // Reductions are fixed-order everywhere (per-wave partial rows / partial tiles -> deep_reduce_all): bit-reproducible results.
 // Reference restated: networks.py:59-70 (forward), neurodiffeq.py:21-34 (diff sweeps), solvers.py:393 (backward).
 #pragma once
 #include "ndq_mlp.h"
-
-#ifndef NDQ_DEEP_XCD_REMAP
-#define NDQ_DEEP_XCD_REMAP 1       // 0: plain blockIdx (A/B runs of the XCD-aware workgroup mapping, xcd_block_id below)
-#endif
-#ifndef NDQ_DEEP_WGRAD_BF
-#define NDQ_DEEP_WGRAD_BF 1        // 0: weight gradients as exact-f32 MFMA products (deep_wgrad_gemm, rounds 4 - 5a); 1: bf16x3 (deep_wgrad_bf)
-#endif
-#ifndef NDQ_DEEP_HEAD_FUSED
-#define NDQ_DEEP_HEAD_FUSED 1      // 0: deep_head_bwd materialises Zbar_L (round 4); 1: its consumers form it from Z_L and the seeds
-#endif
 
 namespace ndq {
 
@@ -227,19 +217,15 @@ __device__ __forceinline__ void first_unit_streams(const real* __restrict__ prm,
 // virtual ids, so a group lands on one XCD, is dispatched within a few ids of each other, and its common rows come out of
 // that XCD's L2.  Bijective for any grid size (q = n / 8, r = n % 8: XCD x owns q + (x < r) ids).
 __device__ __forceinline__ int xcd_block_id() {
-#if NDQ_DEEP_XCD_REMAP
   const int b = (int)blockIdx.x, n = (int)gridDim.x, x = b & 7, q = n >> 3, r = n & 7;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-#else
-  return (int)blockIdx.x;
-#endif
 }
 
 struct DeepArgs {
   const real* coords;     // [D][ldc]
   const real* prm;        // [P]
   int n, np, ldc;         // points, points rounded up to whole tiles, leading dimension of coords
-  const real* wmat;       // padded weight matrix of the layer [HP][HP] (forward: W_l, reverse: W_l^T)
+  const real* wmat;       // unused (the fp32 weight matrix of the retired exact-f32 GEMMs): stays, the kernels' argument offsets depend on it
   const real* bias;       // forward: b_l [W]
   const real* zin;        // forward: Z_{l-1};  reverse: Zbar_l
   const real* zprev;      // reverse: Z_{l-1} (act-backward in the epilogue);  weight gradient: Z_{l-1}
@@ -248,7 +234,7 @@ struct DeepArgs {
   real* pw1;              // reverse into the first layer: partial rows of dW1 [stripes][HP][D]
   real* pw;               // weight gradient: partial tiles [KS][HP][HP]
   const void* wpl;        // bf16x3 route: the layer's weight planes in MFMA A-operand order (deep_prep_planes)
-  // head fused into its consumers (NDQ_DEEP_HEAD_FUSED): Zbar_L = act-backward(Z_L, Wout^T seeds) is never written -- zin is
+  // head fused into its consumers (HP <= 128): Zbar_L = act-backward(Z_L, Wout^T seeds) is never written -- zin is
   // Z_L, and the kernels form Zbar_L from it and the seeds as they load
   const real* gbar;       // [NS][NOUT][ldj] seeds of the output streams
   int ldj;
@@ -259,278 +245,12 @@ struct DeepArgs {
   int ow;                 // forward GEMMs: real width of the layer being computed (its bias has that many entries; DeepCfg::WP)
 };
 
-// ------------------------------------------------------------------------------------------------ per-point GEMMs
-// FIRSTIN: the layer input is the first layer's sigma-jet, evaluated from the coordinates; else sigma-jet(zin).
-// Wave w of the grid owns output chunk w % NCH (JBC blocks of 16 units) and walks the 16-point tiles w / NCH, + stripes.
-#ifndef NDQ_DEEP_OCC
-#define NDQ_DEEP_OCC 1             // workgroups per CU the per-point GEMMs are compiled for (experiments: 2 = 256 registers per wave)
-#endif
-template <class C, bool FIRSTIN>
-__global__ __launch_bounds__(C::THREADS, NDQ_DEEP_OCC) void deep_fwd_gemm(DeepArgs a) {
-  const int lane = threadIdx.x & 63, p = lane & 15, kg = lane >> 4;
-  const int gw = blockIdx.x * C::WAVES + (threadIdx.x >> 6), nw = gridDim.x * C::WAVES;
-  const int ch = gw % C::NCH, stripe = gw / C::NCH, nstripes = nw / C::NCH;
-  if (stripe >= nstripes) return;
-  const int ntiles = a.np >> 4;
-  const size_t sstride = (size_t)a.np * C::HP;
-  // this wave's output units never change: their biases are loaded once (rows 4 kg + r of block b, column p)
-  real4 bs[C::JBC];
-#pragma unroll
-  for (int jb = 0; jb < C::JBC; ++jb) {
-    const int j0 = 16 * (ch * C::JBC + jb) + 4 * kg;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bs[jb][r] = (j0 + r < a.ow) ? a.bias[j0 + r < a.ow ? j0 + r : 0] : 0.f;
-  }
-  for (int tile = stripe; tile < ntiles; tile += nstripes) {
-    const int n = tile * 16 + p;
-    const int nn = n < a.n ? n : a.n - 1;
-    real x[C::D];
-    if constexpr (FIRSTIN) {
-#pragma unroll
-      for (int d = 0; d < C::D; ++d) x[d] = a.coords[(size_t)d * a.ldc + nn];
-    }
-    real4 acc[C::NS][C::JBC];
-#pragma unroll
-    for (int s = 0; s < C::NS; ++s)
-#pragma unroll
-      for (int jb = 0; jb < C::JBC; ++jb) acc[s][jb] = real4{0.f, 0.f, 0.f, 0.f};
-    // the next contraction step's operands are fetched before the current step's MFMAs are issued
-    real4 zn[FIRSTIN ? 1 : C::NS], wn[C::JBC];
-    real f1w[FIRSTIN ? 4 : 1][C::D], f1b[FIRSTIN ? 4 : 1];       // FIRSTIN: first-layer rows of the step's 4 contraction units
-    auto fetch = [&](int c16) {
-      const int k0 = 16 * c16 + 4 * kg;
-      if constexpr (!FIRSTIN) {
-#pragma unroll
-        for (int s = 0; s < C::NS; ++s) zn[s] = *reinterpret_cast<const real4*>(a.zin + s * sstride + (size_t)n * C::HP + k0);
-      } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const bool ok = k0 + t < C::wl(1);
-          f1b[t] = ok ? a.prm[C::offb1 + (ok ? k0 + t : 0)] : 0.f;
-#pragma unroll
-          for (int d = 0; d < C::D; ++d) f1w[t][d] = ok ? a.prm[C::offW1 + (ok ? k0 + t : 0) * C::D + d] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int jb = 0; jb < C::JBC; ++jb) {
-        const int b = ch * C::JBC + jb;
-        wn[jb] = *reinterpret_cast<const real4*>(a.wmat + (size_t)(16 * (b < C::NB ? b : 0) + p) * C::HP + k0);
-      }
-    };
-    fetch(0);
-    for (int c16 = 0; c16 < C::NB; ++c16) {
-      real4 hh[C::NS], w4[C::JBC];
-#pragma unroll
-      for (int jb = 0; jb < C::JBC; ++jb) w4[jb] = wn[jb];
-      {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          real z[C::NS], h[C::NS], tt, cc;
-          if constexpr (FIRSTIN) {
-#pragma unroll
-            for (int s = 0; s < C::NS; ++s) z[s] = 0.f;
-            real zv = f1b[t];
-#pragma unroll
-            for (int d = 0; d < C::D; ++d) {
-              zv = rfma(f1w[t][d], x[d], zv);
-              if constexpr (C::SS::FIRST) z[1 + d] = f1w[t][d];
-            }
-            z[0] = zv;
-          } else {
-#pragma unroll
-            for (int s = 0; s < C::NS; ++s) z[s] = zn[s][t];
-          }
-          jet_unit_forward<C>(z, h, tt, cc);
-#pragma unroll
-          for (int s = 0; s < C::NS; ++s) hh[s][t] = h[s];
-        }
-      }
-      if (c16 + 1 < C::NB) fetch(c16 + 1);
-      __builtin_amdgcn_sched_barrier(0);       // the loads stay ABOVE the MFMAs (the scheduler sinks them below otherwise)
-#pragma unroll
-      for (int jb = 0; jb < C::JBC; ++jb) {
-        const int b = ch * C::JBC + jb;
-        if (b < C::NB) {
-#pragma unroll
-          for (int s = 0; s < C::NS; ++s)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[s][jb] = mfma16x16x4(w4[jb][t], hh[s][t], acc[s][jb]);
-        }
-      }
-    }
-#pragma unroll
-    for (int jb = 0; jb < C::JBC; ++jb) {
-      const int b = ch * C::JBC + jb;
-      if (b < C::NB) {
-        const int j0 = 16 * b + 4 * kg;                    // rows 4 kg + r of the block, column p
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[0][jb][r] += bs[jb][r];
-#pragma unroll
-        for (int s = 0; s < C::NS; ++s) *reinterpret_cast<real4*>(a.zout + s * sstride + (size_t)n * C::HP + j0) = acc[s][jb];
-      }
-    }
-  }
-}
-
-// Hbar_{l-1} = W_l^T Zbar_l, then the act-backward of layer l - 1 in the epilogue.  TOFIRST (l == 2): layer 1's streams come
-// from the coordinates and what leaves is dW1 / db1 (per-wave partial rows); else Zbar_{l-1} is stored and db_{l-1} summed.
-template <class C, bool TOFIRST>
-__global__ __launch_bounds__(C::THREADS, NDQ_DEEP_OCC) void deep_bwd_gemm(DeepArgs a) {
-  constexpr int JB = TOFIRST ? C::JBF : C::JBB, NCH = TOFIRST ? C::NCHF : C::NCHB;
-  const int lane = threadIdx.x & 63, p = lane & 15, kg = lane >> 4;
-  const int gw = blockIdx.x * C::WAVES + (threadIdx.x >> 6), nw = gridDim.x * C::WAVES;
-  const int ch = gw % NCH, stripe = gw / NCH, nstripes = nw / NCH;
-  if (stripe >= nstripes) return;
-  const int ntiles = a.np >> 4;
-  const size_t sstride = (size_t)a.np * C::HP;
-  // TOFIRST: the first layer's rows of this wave's output units (they never change), loaded once
-  real u1w[TOFIRST ? JB : 1][4][C::D], u1b[TOFIRST ? JB : 1][4];
-  if constexpr (TOFIRST) {
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int k = 16 * (ch * JB + jb) + 4 * kg + r;
-        const bool ok = k < C::wl(1);
-        u1b[jb][r] = ok ? a.prm[C::offb1 + (ok ? k : 0)] : 0.f;
-#pragma unroll
-        for (int d = 0; d < C::D; ++d) u1w[jb][r][d] = ok ? a.prm[C::offW1 + (ok ? k : 0) * C::D + d] : 0.f;
-      }
-  }
-  real gb[JB][4], gw1[TOFIRST ? JB : 1][4][C::D];
-#pragma unroll
-  for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      gb[jb][r] = 0.f;
-      if constexpr (TOFIRST) {
-#pragma unroll
-        for (int d = 0; d < C::D; ++d) gw1[jb][r][d] = 0.f;
-      }
-    }
-  for (int tile = stripe; tile < ntiles; tile += nstripes) {
-    const int n = tile * 16 + p;
-    const int nn = n < a.n ? n : a.n - 1;
-    real x[C::D];
-    if constexpr (TOFIRST) {
-#pragma unroll
-      for (int d = 0; d < C::D; ++d) x[d] = a.coords[(size_t)d * a.ldc + nn];
-    }
-    real4 acc[C::NS][JB];
-#pragma unroll
-    for (int s = 0; s < C::NS; ++s)
-#pragma unroll
-      for (int jb = 0; jb < JB; ++jb) acc[s][jb] = real4{0.f, 0.f, 0.f, 0.f};
-    // the epilogue's operands (Z_{l-1} of the tile's output units) are requested up front: they arrive under the MFMAs
-    real4 zpre[TOFIRST ? 1 : JB][C::NS];
-    if constexpr (!TOFIRST) {
-#pragma unroll
-      for (int jb = 0; jb < JB; ++jb) {
-        const int b = ch * JB + jb;
-#pragma unroll
-        for (int s = 0; s < C::NS; ++s)
-          zpre[jb][s] = *reinterpret_cast<const real4*>(a.zprev + s * sstride + (size_t)n * C::HP + 16 * (b < C::NB ? b : 0) + 4 * kg);
-      }
-    }
-    real4 zn[C::NS], wn[JB];
-    auto fetch = [&](int c16) {
-      const int k0 = 16 * c16 + 4 * kg;
-#pragma unroll
-      for (int s = 0; s < C::NS; ++s) zn[s] = *reinterpret_cast<const real4*>(a.zin + s * sstride + (size_t)n * C::HP + k0);
-#pragma unroll
-      for (int jb = 0; jb < JB; ++jb) {
-        const int b = ch * JB + jb;
-        wn[jb] = *reinterpret_cast<const real4*>(a.wmat + (size_t)(16 * (b < C::NB ? b : 0) + p) * C::HP + k0);
-      }
-    };
-    fetch(0);
-    for (int c16 = 0; c16 < C::NB; ++c16) {
-      real4 zb[C::NS], w4[JB];
-#pragma unroll
-      for (int s = 0; s < C::NS; ++s) zb[s] = zn[s];
-#pragma unroll
-      for (int jb = 0; jb < JB; ++jb) w4[jb] = wn[jb];
-      if (c16 + 1 < C::NB) fetch(c16 + 1);
-      __builtin_amdgcn_sched_barrier(0);       // the loads stay ABOVE the MFMAs (the scheduler sinks them below otherwise)
-#pragma unroll
-      for (int jb = 0; jb < JB; ++jb) {
-        const int b = ch * JB + jb;
-        if (b < C::NB) {
-#pragma unroll
-          for (int s = 0; s < C::NS; ++s)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[s][jb] = mfma16x16x4(w4[jb][t], zb[s][t], acc[s][jb]);
-        }
-      }
-    }
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb) {
-      const int b = ch * JB + jb;
-      if (b < C::NB) {
-        const int j0 = 16 * b + 4 * kg;
-        real4 out[C::NS];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          real z[C::NS], g[C::NS], tt, cc;
-          if constexpr (TOFIRST) {
-#pragma unroll
-            for (int s = 0; s < C::NS; ++s) z[s] = 0.f;
-            real zv = u1b[jb][r];
-#pragma unroll
-            for (int d = 0; d < C::D; ++d) {
-              zv = rfma(u1w[jb][r][d], x[d], zv);
-              if constexpr (C::SS::FIRST) z[1 + d] = u1w[jb][r][d];
-            }
-            z[0] = zv;
-          } else {
-#pragma unroll
-            for (int s = 0; s < C::NS; ++s) z[s] = zpre[jb][s][r];
-          }
-          Act<C::ACT>::fwd(z[0], tt, cc);
-#pragma unroll
-          for (int s = 0; s < C::NS; ++s) g[s] = acc[s][jb][r];
-          jet_unit_backward<C>(z, tt, cc, g);
-          gb[jb][r] += g[0];
-          if constexpr (TOFIRST) {
-#pragma unroll
-            for (int d = 0; d < C::D; ++d) gw1[jb][r][d] += C::SS::FIRST ? rfma(g[0], x[d], g[C::SS::FIRST ? 1 + d : 0]) : g[0] * x[d];
-          } else {
-#pragma unroll
-            for (int s = 0; s < C::NS; ++s) out[s][r] = g[s];
-          }
-        }
-        if constexpr (!TOFIRST) {
-#pragma unroll
-          for (int s = 0; s < C::NS; ++s) *reinterpret_cast<real4*>(a.zout + s * sstride + (size_t)n * C::HP + j0) = out[s];
-        }
-      }
-    }
-  }
-  // the 16 points of a tile are one DPP row: fixed-order sums, lanes p == 0 write this wave's partial row
-#pragma unroll
-  for (int jb = 0; jb < JB; ++jb) {
-    const int b = ch * JB + jb;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const real v = point_sum(gb[jb][r]);
-      if (b < C::NB && p == 0) a.pb[(size_t)stripe * C::HP + 16 * b + 4 * kg + r] = v;
-      if constexpr (TOFIRST) {
-#pragma unroll
-        for (int d = 0; d < C::D; ++d) {
-          const real u = point_sum(gw1[jb][r][d]);
-          if (b < C::NB && p == 0) a.pw1[((size_t)stripe * C::HP + 16 * b + 4 * kg + r) * C::D + d] = u;
-        }
-      }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ per-point GEMMs, bf16x3
-// The same products as deep_fwd_gemm / deep_bwd_gemm on the REAL matrix core: v_mfma_f32_16x16x32_bf16 with 3-way split
+// Z_l = W_l sigma-jet(Z_{l-1}) + b_l and Hbar_{l-1} = W_l^T Zbar_l on the REAL matrix core: v_mfma_f32_16x16x32_bf16 with 3-way split
 // operands (x = x0 + x1 + x2, six significant plane products accumulated in fp32, smallest first: fp32-class accuracy,
 // csrc/ndq_mlp.h) -- 6 MFMAs of 16 cycles per 32-deep contraction chunk against 8 exact-f32 MFMAs of 32 cycles, and they
 // overlap with the VALU work of the operand prologue (the f32 MFMA shares the VALU datapath).
-//   weights   deep_prep writes every hidden matrix (and its transpose) as bf16x3 planes in MFMA A-operand order:
+//   weights   deep_prep_planes writes every hidden matrix (and its transpose) as bf16x3 planes in MFMA A-operand order:
 //             element ((b * NCK + c) * 3 + plane) * 64 + lane = the 8 bf16 of row 16 b + (lane & 15), columns
 //             32 c + 8 (lane >> 4) ... + 7.  A workgroup keeps the planes of ITS output chunk (JBR blocks x all NCK
 //             contraction chunks, <= 96 KB) resident in LDS for the whole launch: staged once, read by all four waves.
@@ -931,210 +651,21 @@ __global__ __launch_bounds__(256) void deep_prep_planes(const real* __restrict__
   }
 }
 
-// dW_l[j][k] = sum_{s, n} Zbar_l[s][n][j] sigma-jet(Z_{l-1})[s][n][k]: the contraction runs over points, 4 per MFMA
-// (contraction slot kg of a lane = point 4 g + kg of point group g).
+// ------------------------------------------------------------------------------------------------ weight gradients, bf16x3
+// dW_l[j][k] = sum_{s, n} Zbar_l[s][n][j] sigma-jet(Z_{l-1})[s][n][k] on the bf16 matrix core (round 5).
 // A workgroup owns a 64 x 64 tile of dW_l (tile blockIdx % NT^2) and the slice blockIdx / NT^2 of the point groups, which
 // its four waves walk interleaved; their accumulators are added in wave order through LDS, so one partial tile leaves per
 // workgroup.  A lane's 4 rows (columns) of the tile are the 4 CONSECUTIVE units it loads as one 16-byte value: MFMA block u
-// of the tile = units {4 i + u}, a relabelling of rows that costs nothing.  The next group's loads are issued before the
-// current group's MFMAs (the kernel has ~60 registers: 4 workgroups per CU hide the rest of the latency).
-// HEAD (layer L with the head folded in, NDQ_DEEP_HEAD_FUSED): zin is Z_L; the row operand Zbar_L = act-backward(Z_L, Wout^T
-// seeds) is formed per lane from its 4 units of its point, and the tiles of column block 0 also leave what deep_head_bwd used
-// to: partial rows of dWout (seeds x sigma-jet(Z_L)), db_L (value stream of Zbar_L) and -- tile 0 -- dbout, one per wave.
-template <class C, bool FIRSTIN, bool HEAD = false>
-__global__ __launch_bounds__(C::THREADS, 2) void deep_wgrad_gemm(DeepArgs a) {
-  __shared__ real comb[3][64][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, kg = lane >> 4;
-  constexpr int NT2 = C::NT * C::NT;
-  const int vid = xcd_block_id();                          // (the NT x NT tiles of a point slice share its rows: one XCD)
-  const int tl = vid % NT2, ks = vid / NT2, KS = gridDim.x / NT2;
-  if (ks >= KS) return;
-  const int j0 = 64 * (tl / C::NT) + 4 * i, k0 = 64 * (tl % C::NT) + 4 * i;      // this lane's 4 row / column units
-  const bool jok = j0 < C::HP, kok = k0 < C::HP;
-  const size_t sstride = (size_t)a.np * C::HP;
-  real4 acc[4][4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc[u][v] = real4{0.f, 0.f, 0.f, 0.f};
-  // FIRSTIN: the first layer's rows of this lane's 4 column units
-  real w1v[FIRSTIN ? 4 : 1][C::D], b1v[FIRSTIN ? 4 : 1];
-  if constexpr (FIRSTIN) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const bool ok = k0 + v < C::wl(1);
-      b1v[v] = ok ? a.prm[C::offb1 + (ok ? k0 + v : 0)] : 0.f;
-#pragma unroll
-      for (int d = 0; d < C::D; ++d) w1v[v][d] = ok ? a.prm[C::offW1 + (ok ? k0 + v : 0) * C::D + d] : 0.f;
-    }
-  }
-  const int ngroups = a.np >> 2, g0 = ks * C::WAVES + wave, gstep = KS * C::WAVES;
-  real4 za[C::NS], zk[FIRSTIN ? 1 : C::NS];
-  real x[FIRSTIN ? C::D : 1];
-  // HEAD: Wout columns of this lane's 4 row units, the point's seeds (prefetched with the rows), the by-products
-  const bool side = HEAD && (tl % C::NT) == 0;
-  real wov[HEAD ? 4 : 1][C::NOUT], gsn[HEAD ? C::NC : 1], dwo[HEAD ? 4 : 1][C::NOUT], dbl[HEAD ? 4 : 1], gbo[HEAD ? C::NOUT : 1];
-  if constexpr (HEAD) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const bool ok = j0 + v < C::wl(C::L);
-      dbl[v] = 0.f;
-#pragma unroll
-      for (int o = 0; o < C::NOUT; ++o) {
-        wov[v][o] = ok ? a.prm[C::offWout + o * C::wl(C::L) + (ok ? j0 + v : 0)] : 0.f;
-        dwo[v][o] = 0.f;
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < C::NOUT; ++o) gbo[o] = 0.f;
-  }
-  auto fetch = [&](int g4) {
-    const int n = 4 * g4 + kg;
-    if constexpr (HEAD) {
-      const int ns = n < a.n ? n : a.n - 1;
-#pragma unroll
-      for (int cc = 0; cc < C::NC; ++cc) gsn[cc] = n < a.n ? a.gbar[(size_t)cc * a.ldj + ns] : 0.f;
-    }
-#pragma unroll
-    for (int s = 0; s < C::NS; ++s)
-      za[s] = jok ? *reinterpret_cast<const real4*>(a.zin + s * sstride + (size_t)n * C::HP + j0) : real4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (FIRSTIN) {
-      const int nn = n < a.n ? n : a.n - 1;
-#pragma unroll
-      for (int d = 0; d < C::D; ++d) x[d] = a.coords[(size_t)d * a.ldc + nn];
-    } else {
-#pragma unroll
-      for (int s = 0; s < C::NS; ++s)
-        zk[s] = kok ? *reinterpret_cast<const real4*>(a.zprev + s * sstride + (size_t)n * C::HP + k0) : real4{0.f, 0.f, 0.f, 0.f};
-    }
-  };
-  if (g0 < ngroups) fetch(g0);
-  for (int g4 = g0; g4 < ngroups; g4 += gstep) {
-    real4 av[C::NS], hv[C::NS];
-    if constexpr (HEAD) {
-#pragma unroll
-      for (int o = 0; o < C::NOUT; ++o) gbo[o] += gsn[o];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        real z[C::NS], g[C::NS], h[C::NS], tt, cc;
-#pragma unroll
-        for (int s = 0; s < C::NS; ++s) {
-          z[s] = za[s][v];
-          real w = 0.f;
-#pragma unroll
-          for (int o = 0; o < C::NOUT; ++o) w = rfma(wov[v][o], gsn[s * C::NOUT + o], w);
-          g[s] = w;
-        }
-        if (side) {                                        // (workgroup-uniform)
-          jet_unit_forward<C>(z, h, tt, cc);
-#pragma unroll
-          for (int s = 0; s < C::NS; ++s)
-#pragma unroll
-            for (int o = 0; o < C::NOUT; ++o) dwo[v][o] = rfma(gsn[s * C::NOUT + o], h[s], dwo[v][o]);
-        } else {
-          Act<C::ACT>::fwd(z[0], tt, cc);
-        }
-        jet_unit_backward<C>(z, tt, cc, g);
-        dbl[v] += g[0];
-#pragma unroll
-        for (int s = 0; s < C::NS; ++s) av[s][v] = g[s];
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < C::NS; ++s) av[s] = za[s];
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      real z[C::NS], h[C::NS], tt, cc;
-      if constexpr (FIRSTIN) {
-#pragma unroll
-        for (int s = 0; s < C::NS; ++s) z[s] = 0.f;
-        real zv = b1v[v];
-#pragma unroll
-        for (int d = 0; d < C::D; ++d) {
-          zv = rfma(w1v[v][d], x[d], zv);
-          if constexpr (C::SS::FIRST) z[1 + d] = w1v[v][d];
-        }
-        z[0] = zv;
-      } else {
-#pragma unroll
-        for (int s = 0; s < C::NS; ++s) z[s] = zk[s][v];
-      }
-      jet_unit_forward<C>(z, h, tt, cc);
-#pragma unroll
-      for (int s = 0; s < C::NS; ++s) hv[s][v] = h[s];
-    }
-    if (g4 + gstep < ngroups) fetch(g4 + gstep);           // in flight under the MFMAs below
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int s = 0; s < C::NS; ++s)
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[u][v] = mfma16x16x4(av[s][u], hv[s][v], acc[u][v]);
-  }
-  if constexpr (HEAD) {
-    // by-products: one partial row per WAVE; a lane's sums run over the points with contraction slot kg -> + the 4 slots
-    const int row = ks * C::WAVES + wave;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const real db = quad_sum(dbl[v]);
-      if (side && kg == 0 && j0 + v < C::HP) a.pbh[(size_t)row * C::HP + j0 + v] = db;
-#pragma unroll
-      for (int o = 0; o < C::NOUT; ++o) {
-        const real dw = quad_sum(dwo[v][o]);
-        if (side && kg == 0 && j0 + v < C::HP) a.pwo[((size_t)row * C::NOUT + o) * C::HP + j0 + v] = dw;
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < C::NOUT; ++o) {
-      const real gb = quad_sum(gbo[o]);
-      if (tl == 0 && lane == 0) a.pbo[(size_t)row * C::NOUT + o] = gb;
-    }
-  }
-  // waves 1 .. 3 -> LDS, wave 0 adds them in order and stores the workgroup's partial tile
-  if (wave > 0) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) comb[wave - 1][(u * 4 + v) * 4 + r][lane] = acc[u][v][r];
-  }
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll 1
-    for (int w = 0; w < 3; ++w)
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[u][v][r] += comb[w][(u * 4 + v) * 4 + r][lane];
-    // D layout: register r of lane (i, kg) = row 4 kg + r, column i of the 16 x 16 block (u, v):
-    // row unit = 64 tj + 4 (4 kg + r) + u, column units 64 tk + 4 i + v, v = 0 .. 3 -- one 16-byte store
-    real* out = a.pw + (size_t)ks * C::HP * C::HP;
-    const int jbase = 64 * (tl / C::NT);
-    if (kok) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = jbase + 4 * (4 * kg + r) + u;
-          if (row < C::HP)
-            *reinterpret_cast<real4*>(out + (size_t)row * C::HP + k0) = real4{acc[u][0][r], acc[u][1][r], acc[u][2][r], acc[u][3][r]};
-        }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ weight gradients, bf16x3
-// dW_l on the bf16 matrix core (round 5).  Same tiling, same loads and the same per-lane arithmetic in front of the products as
-// deep_wgrad_gemm; what changes is the product: v_mfma_f32_16x16x32_bf16 contracts 32 slots per instruction, 8 per lane.  The
+// of the tile = units {4 i + u}, a relabelling of rows that costs nothing.
+// HEAD (layer L with the head folded in, HP <= 128): zin is Z_L; the row operand Zbar_L = act-backward(Z_L, Wout^T
+// seeds) is formed per lane from its 4 units of its point, and the tiles of column block 0 also leave what deep_head_bwd
+// leaves at the wider shapes: partial rows of dWout (seeds x sigma-jet(Z_L)), db_L (value stream of Zbar_L) and -- tile 0 --
+// dbout, one per wave.
+// The product: v_mfma_f32_16x16x32_bf16 contracts 32 slots per instruction, 8 per lane.  The
 // contraction index of dW_l = sum_{s, n} Zbar_l[s][n][j] H_{l-1}[s][n][k] is the PAIR (point, stream), and any order of it
 // serves as long as both operands agree -- so a lane's 8 slots of a chunk are simply the next 8 (group, stream) values it
 // produces: point group g hands every lane (i, kg) the NS stream values of point 4 g + kg for its 4 row units and its 4 column
-// units (two 16-byte loads per stream, as before), they are split two at a time into three bf16 planes (x = x0 + x1 + x2) and
+// units (two 16-byte loads per stream), they are split two at a time into three bf16 planes (x = x0 + x1 + x2) and
 // written into the chunk's next two slots; a full chunk issues the six significant plane products for the 4 x 4 blocks of the
 // tile.  U = 8 / gcd(8, NS) groups (at least 2) fill whole chunks: a ROUND of U groups is straight-line code, so every slot
 // index is a compile-time constant and nothing is transposed anywhere.  6 products of 16 cycles per 8 slots against 8
@@ -1510,19 +1041,6 @@ __global__ __launch_bounds__(C::THREADS) void deep_head_bwd(DeepHeadArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ helpers
-// padded copies of the hidden weight matrices: wp[l - 2] = W_l (HP x HP, zero padding), wt[l - 2] = W_l^T
-template <class C>
-__global__ __launch_bounds__(256) void deep_prep(const real* __restrict__ prm, real* __restrict__ wp, real* __restrict__ wt) {
-  const int l = 2 + blockIdx.y;
-  const size_t base = (size_t)(l - 2) * C::HP * C::HP;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < C::HP * C::HP; e += gridDim.x * blockDim.x) {
-    const int j = e / C::HP, k = e % C::HP;
-    const real v = (j < C::wl(l) && k < C::wl(l - 1)) ? prm[C::offW(l) + j * C::wl(l - 1) + k] : 0.f;
-    wp[base + e] = v;
-    wt[base + (size_t)k * C::HP + j] = v;
-  }
-}
-
 // Second stage of every reduction of a reverse sweep in ONE launch.  Job k: dst[r * cols + c] = sum_{i < nparts}
 // src[(i * rows_p + r) * cols_p + c] (partial rows / tiles written by the kernels above; the padding of rows_p x cols_p is
 // dropped).  Fixed order: thread (x, y) of a 64 x 16 block adds the parts i = y, y + 16, ... of element x in four

@@ -162,12 +162,9 @@ kernels_record make_wide_kernels() {
 // owns that workspace (hipMalloc on first use, grown when a larger batch arrives, never inside a timed steady state); the
 // adjoint entry recomputes the forward layers like every ndq_mlp_jet_bwd and writes ONE row of "partials" -- the gradient
 // itself, its own reductions being fixed-order already (bwd_waves is set so that ndq_mlp_bwd_blocks() == 1).
-#ifndef NDQ_DEEP_BF16X3
-#define NDQ_DEEP_BF16X3 1          // per-point GEMMs of the deep wide networks on the bf16 matrix core with 3-way split operands
-#endif                             // (0: the exact-f32 MFMA kernels -- A/B runs, and the fallback the first version shipped with)
 struct DeepPlan {
   int np, blocks_max;
-  size_t X, z0, zb0, wp, wt, pw, pw_layer, pb, pb_layer, pw1, pwo, pbo, wpl, wtl, planes_layer, total;
+  size_t X, z0, zb0, pw, pw_layer, pb, pb_layer, pw1, pwo, pbo, wpl, wtl, planes_layer, total;
 };
 template <class K>
 int deep_set_lds(K kernel, size_t bytes) {
@@ -183,8 +180,6 @@ DeepPlan deep_plan(int n) {
   size_t o = 0;
   q.z0 = o; o += (size_t)(C::L - 1) * q.X;            // Z_2 .. Z_L
   q.zb0 = o; o += 2 * q.X;                            // Zbar ping-pong
-  q.wp = o; o += (size_t)(C::L - 1) * HP * HP;
-  q.wt = o; o += (size_t)(C::L - 1) * HP * HP;
   q.pw_layer = (2 * (size_t)q.blocks_max / (C::NT * C::NT) + 1) * HP * HP;       // per hidden matrix
   q.pw = o; o += (size_t)(C::L - 1) * q.pw_layer;
   q.pb_layer = nwmax * HP;                                                          // per hidden layer
@@ -231,15 +226,11 @@ inline int deep_blocks(long waves, int min_waves, int cap) {
 // forward layers 2 .. L into the workspace (shared by the two entry points)
 // jets != nullptr (forward entry point): when one output chunk holds all units (NCH == 1: W <= 128) the LAST layer's GEMM
 // also computes the output streams (deep_gemm_bf EPI 3) and the caller skips deep_head_fwd; returns 1 in *head_done then.
-#ifndef NDQ_DEEP_HEAD_FWD_FUSED
-#define NDQ_DEEP_HEAD_FWD_FUSED 1
-#endif
 template <class C>
 int deep_forward_layers(const DeepPlan& q, real* ws, const real* coords, int ldc, int n, const real* params, hipStream_t st,
                         real* jets = nullptr, int ldj = 0, int* head_done = nullptr) {
   const int ntiles = q.np / 16;
   if (head_done) *head_done = 0;
-#if NDQ_DEEP_BF16X3
   hipLaunchKernelGGL(deep_prep_planes<C>, dim3(64, C::L - 1), dim3(256), 0, st, params, reinterpret_cast<bf16x8*>(ws + q.wpl),
                      reinterpret_cast<bf16x8*>(ws + q.wtl));
   constexpr int NCHB0 = (C::NB + deep_bf_jb<C, 0>() - 1) / deep_bf_jb<C, 0>();
@@ -247,7 +238,7 @@ int deep_forward_layers(const DeepPlan& q, real* ws, const real* coords, int ldc
   if (!attr) {
     int e = deep_set_lds(&deep_gemm_bf<C, 0, 0>, deep_bf_lds_bytes<C, 0>());
     if (!e) e = deep_set_lds(&deep_gemm_bf<C, 1, 0>, deep_bf_lds_bytes<C, 0>());
-    if constexpr (NCHB0 == 1 && NDQ_DEEP_HEAD_FWD_FUSED) {
+    if constexpr (NCHB0 == 1) {
       if (!e) e = deep_set_lds(&deep_gemm_bf<C, 0, 3>, deep_bf_lds_bytes<C, 0>());
       if (!e) e = deep_set_lds(&deep_gemm_bf<C, 1, 3>, deep_bf_lds_bytes<C, 0>());
     }
@@ -257,22 +248,16 @@ int deep_forward_layers(const DeepPlan& q, real* ws, const real* coords, int ldc
   int stripes = (ntiles + kDeepBfWaves - 1) / kDeepBfWaves;                              // one workgroup per CU: its weight planes fill the LDS
   if (stripes > kDeepBfOcc * q.blocks_max / NCHB0) stripes = kDeepBfOcc * q.blocks_max / NCHB0;
   if (stripes < 1) stripes = 1;
-#else
-  hipLaunchKernelGGL(deep_prep<C>, dim3(64, C::L - 1), dim3(256), 0, st, params, ws + q.wp, ws + q.wt);
-  const int blocks = deep_blocks((long)ntiles * C::NCH, C::NCH, 2 * q.blocks_max);      // two workgroups per CU
-#endif
   for (int l = 2; l <= C::L; ++l) {
     DeepArgs a{};
     a.coords = coords; a.prm = params; a.n = n; a.np = q.np; a.ldc = ldc;
-    a.wmat = ws + q.wp + (size_t)(l - 2) * C::HP * C::HP;
     a.wpl = ws + q.wpl + (size_t)(l - 2) * q.planes_layer;
     a.bias = params + C::offb(l);
     a.ow = C::wl(l);
     a.zin = l > 2 ? ws + q.z0 + (size_t)(l - 3) * q.X : nullptr;
     a.zout = ws + q.z0 + (size_t)(l - 2) * q.X;
-#if NDQ_DEEP_BF16X3
     bool folded = false;
-    if constexpr (NCHB0 == 1 && NDQ_DEEP_HEAD_FWD_FUSED) {
+    if constexpr (NCHB0 == 1) {
       if (jets && l == C::L) {
         a.jets = jets; a.ldj = ldj;
         if (l == 2) hipLaunchKernelGGL((deep_gemm_bf<C, 0, 3>), dim3(stripes), dim3(kDeepBfThreads), (deep_bf_lds_bytes<C, 0>()), st, a);
@@ -284,10 +269,6 @@ int deep_forward_layers(const DeepPlan& q, real* ws, const real* coords, int ldc
     if (folded) continue;
     if (l == 2) hipLaunchKernelGGL((deep_gemm_bf<C, 0, 0>), dim3(stripes * NCHB0), dim3(kDeepBfThreads), (deep_bf_lds_bytes<C, 0>()), st, a);
     else hipLaunchKernelGGL((deep_gemm_bf<C, 1, 0>), dim3(stripes * NCHB0), dim3(kDeepBfThreads), (deep_bf_lds_bytes<C, 0>()), st, a);
-#else
-    if (l == 2) hipLaunchKernelGGL((deep_fwd_gemm<C, true>), dim3(blocks), dim3(C::THREADS), 0, st, a);
-    else hipLaunchKernelGGL((deep_fwd_gemm<C, false>), dim3(blocks), dim3(C::THREADS), 0, st, a);
-#endif
   }
   return (int)hipGetLastError();
 }
@@ -333,7 +314,7 @@ int deep_kernels_bwd(const real* coords, int ldc, int n, const real* params, con
     J.nblocks += (rows * cols + 63) / 64;
   };
   constexpr int UG = (C::HP + 63) / 64;
-  if (!NDQ_DEEP_HEAD_FUSED || C::HP > 128) {
+  if (C::HP > 128) {
     DeepHeadArgs h{};
     h.prm = params; h.z = ws + q.z0 + (size_t)(C::L - 2) * q.X; h.gbar = gbar; h.zbar = ws + q.zb0;
     h.pwo = ws + q.pwo; h.pb = ws + q.pb + (size_t)(C::L - 1) * q.pb_layer; h.pbo = ws + q.pbo; h.n = n; h.np = q.np; h.ldj = ldj;
@@ -351,7 +332,6 @@ int deep_kernels_bwd(const real* coords, int ldc, int n, const real* params, con
     a.coords = coords; a.prm = params; a.n = n; a.np = q.np; a.ldc = ldc;
     a.zin = ws + q.zb0 + (size_t)cur * q.X;                               // Zbar_l
     a.zprev = l > 2 ? ws + q.z0 + (size_t)(l - 3) * q.X : nullptr;        // Z_{l-1}
-#if NDQ_DEEP_HEAD_FUSED
     // layer L with the head folded in: no deep_head_bwd pass, no Zbar_L in HBM -- both consumers read Z_L and the seeds.
     // Only where every consumer forms a unit's Zbar_L ONCE (HP <= 128: one output chunk in the reverse GEMM, 2 x 2 tiles in the
     // weight-gradient GEMM); at W = 256 the same arithmetic would be repeated by 4 chunks and 4 tile columns -- measured
@@ -362,47 +342,33 @@ int deep_kernels_bwd(const real* coords, int ldc, int n, const real* params, con
       a.gbar = gbar; a.ldj = ldj;
       a.pwo = ws + q.pwo; a.pbh = ws + q.pb + (size_t)(C::L - 1) * q.pb_layer; a.pbo = ws + q.pbo;
     }
-#else
-    constexpr bool head = false;
-#endif
     {   // dW_l
       a.pw = ws + q.pw + (size_t)(l - 2) * q.pw_layer;
       // one workgroup per (tile, point slice)
       int KS = (q.np / 4 + C::WAVES - 1) / C::WAVES;
-#if NDQ_DEEP_WGRAD_BF
-      constexpr int kWgOcc = deep_wgbf_occ(C::NS);         // bf16x3 products (deep_wgrad_bf)
-#define NDQ_WGRAD_KERNEL deep_wgrad_bf
-#else
-      constexpr int kWgOcc = 2;                            // exact-f32 products (deep_wgrad_gemm): two workgroups per CU
-#define NDQ_WGRAD_KERNEL deep_wgrad_gemm
-#endif
+      constexpr int kWgOcc = deep_wgbf_occ(C::NS);
       if (KS > kWgOcc * q.blocks_max / (C::NT * C::NT)) KS = kWgOcc * q.blocks_max / (C::NT * C::NT);
       if (KS < 1) KS = 1;
       const int blocks = KS * C::NT * C::NT;
       if (head) {
-        if (l == 2) hipLaunchKernelGGL((NDQ_WGRAD_KERNEL<C, true, true>), dim3(blocks), dim3(C::THREADS), 0, st, a);
-        else hipLaunchKernelGGL((NDQ_WGRAD_KERNEL<C, false, true>), dim3(blocks), dim3(C::THREADS), 0, st, a);
+        if (l == 2) hipLaunchKernelGGL((deep_wgrad_bf<C, true, true>), dim3(blocks), dim3(C::THREADS), 0, st, a);
+        else hipLaunchKernelGGL((deep_wgrad_bf<C, false, true>), dim3(blocks), dim3(C::THREADS), 0, st, a);
         reduce(a.pwo, KS * C::WAVES, C::NOUT, C::HP, C::NOUT, C::wl(C::L), grad + C::offWout);
         reduce(a.pbh, KS * C::WAVES, 1, C::HP, 1, C::wl(C::L), grad + C::offb(C::L));
         reduce(a.pbo, KS * C::WAVES, 1, C::NOUT, 1, C::NOUT, grad + C::offbout);
-      } else if (l == 2) hipLaunchKernelGGL((NDQ_WGRAD_KERNEL<C, true>), dim3(blocks), dim3(C::THREADS), 0, st, a);
-      else hipLaunchKernelGGL((NDQ_WGRAD_KERNEL<C, false>), dim3(blocks), dim3(C::THREADS), 0, st, a);
-#undef NDQ_WGRAD_KERNEL
+      } else if (l == 2) hipLaunchKernelGGL((deep_wgrad_bf<C, true>), dim3(blocks), dim3(C::THREADS), 0, st, a);
+      else hipLaunchKernelGGL((deep_wgrad_bf<C, false>), dim3(blocks), dim3(C::THREADS), 0, st, a);
       reduce(a.pw, KS, C::HP, C::HP, C::wl(l), C::wl(l - 1), grad + C::offW(l));
     }
-    a.wmat = ws + q.wt + (size_t)(l - 2) * C::HP * C::HP;
     a.wpl = ws + q.wtl + (size_t)(l - 2) * q.planes_layer;               // planes of W_l^T
     a.pb = ws + q.pb + (size_t)(l - 2) * q.pb_layer;                      // db_{l-1}
-#if NDQ_DEEP_BF16X3
     {
       static bool attr = false;
       if (!attr) {
         int e = deep_set_lds(&deep_gemm_bf<C, 2, 1>, deep_bf_lds_bytes<C, 1>());
         if (!e) e = deep_set_lds(&deep_gemm_bf<C, 2, 2>, deep_bf_lds_bytes<C, 2>());
-#if NDQ_DEEP_HEAD_FUSED
         if (!e) e = deep_set_lds(&deep_gemm_bf<C, 3, 1>, deep_bf_lds_bytes<C, 1>());
         if (!e) e = deep_set_lds(&deep_gemm_bf<C, 3, 2>, deep_bf_lds_bytes<C, 2>());
-#endif
         if (e) return e;
         attr = true;
       }
@@ -429,22 +395,6 @@ int deep_kernels_bwd(const real* coords, int ldc, int n, const real* params, con
       reduce(a.pb, stripes * kDeepBfWaves, 1, C::HP, 1, C::wl(1), grad + C::offb1);
       reduce(a.pw1, stripes * kDeepBfWaves, C::HP, C::D, C::wl(1), C::D, grad + C::offW1);
     }
-#else
-    if (l > 2) {
-      a.zout = ws + q.zb0 + (size_t)(cur ^ 1) * q.X;
-      const int blocks = deep_blocks((long)ntiles * C::NCHB, C::NCHB, 2 * q.blocks_max);
-      hipLaunchKernelGGL((deep_bwd_gemm<C, false>), dim3(blocks), dim3(C::THREADS), 0, st, a);
-      reduce(a.pb, blocks * C::WAVES / C::NCHB, 1, C::HP, 1, C::wl(l - 1), grad + C::offb(l - 1));
-      cur ^= 1;
-    } else {
-      a.pw1 = ws + q.pw1;
-      const int blocks = deep_blocks((long)ntiles * C::NCHF, C::NCHF, 2 * q.blocks_max);
-      const int stripes = blocks * C::WAVES / C::NCHF;
-      hipLaunchKernelGGL((deep_bwd_gemm<C, true>), dim3(blocks), dim3(C::THREADS), 0, st, a);
-      reduce(a.pb, stripes, 1, C::HP, 1, C::wl(1), grad + C::offb1);
-      reduce(a.pw1, stripes, C::HP, C::D, C::wl(1), C::D, grad + C::offW1);
-    }
-#endif
   }
   hipLaunchKernelGGL(deep_reduce_all, dim3(J.nblocks), dim3(64, 16), 0, st, J);
   return (int)hipGetLastError();

@@ -306,9 +306,38 @@ constexpr bool act_has_s4(int act) {
   return act == ACT_TANH || act == ACT_SIN || act == ACT_SIGMOID || act == ACT_ELU || act == ACT_SOFTPLUS || act == ACT_GELU;
 }
 
-#ifndef NDQ_FAST_TANH
-#define NDQ_FAST_TANH 1
+// ------------------------------------------------------------------------------------------------ compile-time switches
+// Every switch below is one that something in the tree sets.  (Settled A/B switches were folded into the side that won;
+// the measurement stands at the code that won, the A/B itself is reproducible from the parent of the commit that folded it.)
+//   switch            default  set by                                              the other side is exercised by
+//   NDQ_F64           0        csrc/ndq_api64.hip, fp64 extension / closure modules    tests/test_gpu_f64_*.py, libndq64.so
+//   NDQ_BWD_THREADS   256      codegen.fused_build_plan(threads=512), _canary.py   512: tests/test_gpu_closure_kept_factors.py, test_gpu_epilogue_reduce_scatter.py
+//   NDQ_FWD_THREADS   256      NDQ_JIT_FLAGS / NDQ_LIB_FLAGS                        scripts/variants.py
+//   NDQ_FWD_NPROD     6        NDQ_JIT_FLAGS                                        scripts/variants.py
+//   NDQ_HBAR_NPROD    6        closure modules: 4 (codegen.CLOSURE_PRODUCTS)        every closure test; 6: the C-ABI adjoint kernels
+//   NDQ_WG_NPROD      6        closure modules: 3 (codegen.CLOSURE_PRODUCTS)        every closure test; 6: the C-ABI adjoint kernels
+//   NDQ_WG_TR         0        closure modules: 1 (codegen.py, MODES[...].wg_tr)    0: libndq.so's adjoint kernels, scripts/ablate.py
+//   NDQ_WG_TR_K       1        closure modules: the number of networks              tests/test_gpu_matrix.py (multi-network systems)
+//   NDQ_MULTI_G2      2        NDQ_JIT_FLAGS (4 = two waves per SIMD at K = 2)      scripts/variants.py
+//   NDQ_WIDE_SG       2        NDQ_JIT_FLAGS                                        scripts/variants.py
+//   NDQ_FWD_BF16X1    0        NDQ_LIB_FLAGS=-DNDQ_FWD_BF16X1=1 (a second library)  tests/test_gpu_parity.py, scripts/bf16_forward.py
+//   NDQ_EPILOGUE_RS   1        NDQ_JIT_FLAGS=-DNDQ_EPILOGUE_RS=0 (the build builds both)    tests/test_gpu_epilogue_reduce_scatter.py
+//   NDQ_ABL           0        scripts/ablate.py (wrong results by design)         scripts/ablate.py
+//   NDQ_PHASE_TS      unset    scripts/phase_ts.py, scripts/phase_ts_group.py      the same scripts
+// (the tuning values of the wide and deep kernels -- NDQ_DEEP_BF_*, NDQ_DEEP_WGBF_*, NDQ_WIDE_THREADS, NDQ_*_MAX_BLOCKS -- are
+// parameters and stand where they are used: ndq_deep.h, ndq_wide.h, ndq_launch.h)
+//
+// Retired switches stop the build: a stale NDQ_JIT_FLAGS / NDQ_LIB_FLAGS would otherwise compile the same kernel twice (the
+// flags are part of the cache key) and "measure" noise.  tests/test_retired_switches.py holds the list this block is checked against.
+#if defined(NDQ_FAST_TANH) || defined(NDQ_BF16X3) || defined(NDQ_WIDE_LOWREG) || defined(NDQ_PIN_WEIGHT_READS) || \
+    defined(NDQ_KEEP_H) || defined(NDQ_REUSE_FWD) || defined(NDQ_WIDE_LAUNDER) || defined(NDQ_WG32) || \
+    defined(NDQ_WG_SCHED_BARRIER) || defined(NDQ_QUAD_SWAP) || defined(NDQ_STAGE_INFLIGHT) || defined(NDQ_GROUP_PREFETCH) || \
+    defined(NDQ_WG_BF16) || defined(NDQ_SPLIT_PAIRS) || defined(NDQ_STAGGER) || defined(NDQ_BF16_NPROD) || \
+    defined(NDQ_DEEP_XCD_REMAP) || defined(NDQ_DEEP_HEAD_FUSED) || defined(NDQ_DEEP_HEAD_FWD_FUSED) || \
+    defined(NDQ_DEEP_WGRAD_BF) || defined(NDQ_DEEP_BF16X3)
+#error "retired compile-time switch: NDQ_FAST_TANH, NDQ_BF16X3, NDQ_WIDE_LOWREG, NDQ_PIN_WEIGHT_READS, NDQ_KEEP_H, NDQ_REUSE_FWD, NDQ_WIDE_LAUNDER, NDQ_WG32, NDQ_WG_SCHED_BARRIER, NDQ_QUAD_SWAP, NDQ_STAGE_INFLIGHT, NDQ_GROUP_PREFETCH, NDQ_WG_BF16, NDQ_SPLIT_PAIRS, NDQ_STAGGER, NDQ_BF16_NPROD, NDQ_DEEP_XCD_REMAP, NDQ_DEEP_HEAD_FUSED, NDQ_DEEP_HEAD_FWD_FUSED, NDQ_DEEP_WGRAD_BF and NDQ_DEEP_BF16X3 were folded into the side that won (DESIGN.md); remove the flag"
 #endif
+
 #ifndef NDQ_BWD_THREADS
 // 512 threads (2 waves per SIMD, 256 registers each) measured ~3 % faster on the C2 closure kernel, but every kernel
 // that then spills to scratch (mlp_jet_bwd<2,1,5,..>: 28 VGPRs, <2,1,7,..>: 64) came back with a few corrupted
@@ -317,15 +346,15 @@ constexpr bool act_has_s4(int act) {
 // two scratch-using waves on one SIMD is the common factor -- so: one wave per SIMD.
 #define NDQ_BWD_THREADS 256
 #endif
+#ifndef NDQ_FWD_THREADS
+#define NDQ_FWD_THREADS 256
+#endif
 
 // Hidden-layer GEMMs on the bf16 matrix core with 3-way split operands ("bf16x3"): x = x0 + x1 + x2 (three bf16
 // chunks = 24 mantissa bits), products a0b0 + a0b1 + a1b0 + a0b2 + a2b0 + a1b1 accumulated in fp32 -> relative error
 // ~2^-23, i.e. fp32-class accuracy.  Why: the f32-input MFMA shares the VALU datapath on gfx950 (it does NOT overlap
 // with VALU work -- scripts/ubench_mfma_valu.hip, profiles/archive/r01/r01e_ubench_*), while v_mfma_f32_16x16x32_bf16 runs on the
 // real matrix core, 6 of them replace 8 f32 MFMAs at ~1/3 of the cycles, and they overlap with the activation math.
-#ifndef NDQ_BF16X3
-#define NDQ_BF16X3 1
-#endif
 // Weight gradients: a first bf16x3 variant in round 1 (fragments transposed by MFMAs against 0/1 selection operands,
 // six split products) came out 9e-5 off (rel-L2, C2 closure) and was rejected -- the transposing products themselves
 // went through the bf16 matrix core.  The route of round 3 (Cfg::WG_TR / WG_TR64) transposes the bf16 PLANES through
@@ -341,10 +370,6 @@ constexpr bool act_has_s4(int act) {
 // An operand none of whose consumers reads its third plane is split into TWO planes (a third less splitting work and, for
 // the transposed LDS images of the weight-gradient GEMM, a third less LDS traffic): NDQ_H_PLANES (forward activations),
 // NDQ_HTR_PLANES (their transposed images), NDQ_Z_PLANES (the adjoint operand).
-#ifdef NDQ_BF16_NPROD              // (round-6 experiments: one number for forward and reverse)
-#define NDQ_FWD_NPROD NDQ_BF16_NPROD
-#define NDQ_HBAR_NPROD NDQ_BF16_NPROD
-#endif
 #ifndef NDQ_FWD_NPROD
 #define NDQ_FWD_NPROD 6
 #endif
@@ -385,35 +410,8 @@ constexpr bool act_has_s4(int act) {
 #define NDQ_HTR_PLANES ((NDQ_WG_NPROD == 6) ? 3 : 2)
 #define NDQ_H_PLANES ((NDQ_FWD_NPROD == 6 || NDQ_WG_NPROD == 6) ? 3 : 2)
 #define NDQ_Z_PLANES ((NDQ_HBAR_NPROD == 6 || NDQ_WG_NPROD == 6) ? 3 : 2)
-#ifndef NDQ_WIDE_LOWREG
-#define NDQ_WIDE_LOWREG 1
-#endif
-#ifndef NDQ_PIN_WEIGHT_READS
-#define NDQ_PIN_WEIGHT_READS 1
-#endif
 #ifndef NDQ_WIDE_SG
 #define NDQ_WIDE_SG 2    // streams whose bf16 planes are live at a time in the wide-net GEMMs
-#endif
-#ifndef NDQ_KEEP_H
-#define NDQ_KEEP_H 1
-#endif
-#ifndef NDQ_REUSE_FWD
-#define NDQ_REUSE_FWD 1   // 8-wave closure builds of H = 32 networks (Cfg::REUSE_FWD); 0 = launder the layer states as before
-#endif
-#ifndef NDQ_FWD_THREADS
-#define NDQ_FWD_THREADS 256
-#endif
-#ifndef NDQ_WG_SCHED_BARRIER
-#define NDQ_WG_SCHED_BARRIER 1
-#endif
-// Ablation switches (experiments only, wrong results by design): NDQ_ABL bit 0 = no weight-gradient GEMMs, bit 1 = no
-// hbar GEMM, bit 2 = no forward hidden GEMM, bit 3 = no act_backward, bit 4 = no LDS transposes (MFMAs on stale data),
-// bit 5 = no operand splitting (planes reused).  scripts/ablate.py times the closure kernel with each of them.
-#ifndef NDQ_WIDE_LAUNDER
-#define NDQ_WIDE_LAUNDER 1
-#endif
-#ifndef NDQ_WG_BF16
-#define NDQ_WG_BF16 0     // narrow nets: weight-gradient GEMMs on the bf16 matrix core (split operands) instead of f32 MFMAs
 #endif
 #ifndef NDQ_WG_TR
 #define NDQ_WG_TR 0       // narrow nets, single-launch closure kernels (set by codegen.py for those modules): hidden-layer
@@ -432,35 +430,16 @@ constexpr bool act_has_s4(int act) {
                           // STREAM kernel (mlp_jet_fwd_kernel, three-kernel pipeline) on single bf16 operands -- BASELINE config 5's
                           // "bf16 fwd / fp32 grad"; the adjoint kernels recompute their forward pass in bf16x3 as always
 #endif
-#ifndef NDQ_QUAD_SWAP
-#define NDQ_QUAD_SWAP 1   // quad_sum through v_permlane16/32_swap instead of ds_bpermute: same bits.  Round 5 measured it NOT faster
-                          // (C2 closure 19.5 vs 19.2 us: the LDS round trip was not on the critical path then); with the reverse
-                          // pass's products and planes cut down (round 6) it is: 17.52 -> 17.03 us on one box, 16.23 -> 16.09 on
-                          // another (profiles/r06h_flags_ab_c2.txt, r06j_own_tile_ab.txt) -- on.  0: the ds_bpermute route.
-#endif
 #ifndef NDQ_EPILOGUE_RS
 #define NDQ_EPILOGUE_RS 1 // single-launch closure kernels of H = 32 single-output networks: reduction epilogue with a butterfly
                           // reduce-scatter, dense deposits and swizzled matrix deposits (block_reduce_store_rs); the same
                           // summation trees, so the same bits.  0: block_reduce_store and the separate loss sum, as before
 #endif
-#ifndef NDQ_SPLIT_PAIRS
-#define NDQ_SPLIT_PAIRS 0   // split3 on 2-wide vectors: 3.5 % fewer VALU instructions in C3's closure kernel, no time gained
-                            // (C3 418.4 -> 419.8 us, C2 8-wave 19.9 -> 19.7 us on MI355X): off
-#endif
-#ifndef NDQ_WG32
-#define NDQ_WG32 1        // wide nets: weight-gradient GEMMs as split-operand v_mfma_f32_32x32x16_bf16 (one stream per instruction)
-#endif
+// Ablation switches (experiments only, wrong results by design): NDQ_ABL bit 0 = no weight-gradient GEMMs, bit 1 = no
+// hbar GEMM, bit 2 = no forward hidden GEMM, bit 3 = no act_backward, bit 4 = no LDS transposes (MFMAs on stale data),
+// bit 5 = no operand splitting (planes reused).  scripts/ablate.py times the closure kernel with each of them.
 #ifndef NDQ_ABL
 #define NDQ_ABL 0
-#endif
-#ifndef NDQ_STAGE_INFLIGHT
-#define NDQ_STAGE_INFLIGHT 1   // 0: weight staging array by array (rounds 1 - 4; A/B of stage_weights' in-flight pass)
-#endif
-#ifndef NDQ_GROUP_PREFETCH
-#define NDQ_GROUP_PREFETCH 1   // 0: grouped closure kernel loads a group's coordinates at the top of the group loop (A/B)
-#endif
-#ifndef NDQ_STAGGER
-#define NDQ_STAGGER 0       // s_sleep argument (x 64 cycles) by which waves WAVES/2.. start their tile loop late
 #endif
 
 // tanh z = 1 - 2 / (2^(2 z log2 e) + 1): one v_exp_f32 + one v_rcp_f32 (both ~1 ulp).  Absolute error <= ~1.5e-7
@@ -478,11 +457,7 @@ __device__ __forceinline__ real tanh_fast(real z) {
 template <int ACT> struct Act;
 template <> struct Act<ACT_TANH> {  // nn.Tanh, networks.py:27 default
   static __device__ __forceinline__ void fwd(real z, real& t, real& c, real = 1.f) {
-#if NDQ_FAST_TANH || NDQ_F64
     t = tanh_fast(z);
-#else
-    t = tanhf(z);
-#endif
     c = 0.f;
   }
   static __device__ __forceinline__ real s1(real t, real, real = 1.f) { return rfma(-t, t, 1.f); }
@@ -713,7 +688,7 @@ struct Cfg {
   static constexpr int ldsW1T = 0, ldsb1 = NIN * H;
   static constexpr int ldsLayer0 = NIN * H + H;
   // hidden GEMM operand format: bf16x3 planes (3 x 2 B per weight) when the width is a multiple of 32, else f32
-  static constexpr bool BF16 = (NDQ_BF16X3 != 0) && (NB_ % 2 == 0) && (NDQ_F64 == 0);
+  static constexpr bool BF16 = (NB_ % 2 == 0) && (NDQ_F64 == 0);
   static constexpr int NC = NB_ / 2;                       // K-chunks of 32 contraction slots (bf16 path)
   static constexpr int WEL = BF16 ? (H * H * 3) / 2 : H * H;   // floats of LDS per weight matrix image
   // multi-output networks: the output layer (HO x H, zero-padded rows) runs on the bf16 matrix core as well when its
@@ -722,13 +697,13 @@ struct Cfg {
   static constexpr int NCO = NBO / 2;
   static constexpr int WOEL = BF16O ? (HO * H * 3) / 2 : HO * H;   // floats of LDS per output-layer image
   // (one wave per SIMD only; the source of the two-waves-per-SIMD builds recomputes them -- see LAUNDER below)
-  static constexpr bool KEEP_H = (NB_ == 2) && (NDQ_KEEP_H != 0) && (SS::NS <= 6) && (BWD_THREADS == 256);
+  static constexpr bool KEEP_H = (NB_ == 2) && (SS::NS <= 6) && (BWD_THREADS == 256);
   // wide nets (H >= 64): the reverse pass is register-bound, so (a) the per-point GEMMs go through their bf16 planes
   // SG streams at a time instead of all at once, (b) the bias-type gradient sums (db_l, dW1, dWout: one value per
   // unit) live in a per-wave LDS region instead of registers, (c) the first layer's derivative streams (columns of
   // W1) are re-read from LDS for the reverse pass instead of being kept.  (Recomputing the middle layer's state in
   // the reverse pass instead of keeping it was tried too: no fewer spills, 16 % slower -- rejected.)
-  static constexpr bool WIDE = (NB_ >= 4) && (NDQ_WIDE_LOWREG != 0);
+  static constexpr bool WIDE = (NB_ >= 4);
   // ... and the 8-wave builds of narrow nets (256 registers per wave) run the reverse GEMM two streams at a time as well
   static constexpr bool GROUP_HBAR = WIDE || (BWD_THREADS != 256 && SS::NS > 2);
   static constexpr int SG = GROUP_HBAR ? NDQ_WIDE_SG : SS::NS;
@@ -749,16 +724,12 @@ struct Cfg {
   static constexpr int ldsWeightsEnd(bool bwd) { return (ldsAlpha(bwd) + (ALPHA ? L : 0) + 3) & ~3; }
   // weight-gradient transposes: streams staged per barrier round (narrow nets: two at a time, so that the LDS round
   // trip of one stream hides behind the MFMAs of the other; wide nets: no LDS to spare)
-  // WG_BF16 (narrow nets on the bf16x3 path): the weight-gradient GEMM dW += sum_s Zbar_s H_s^T runs on
-  // v_mfma_f32_16x16x32_bf16 as well -- one instruction contracts over 32 slots = 2 streams x 16 points, so two streams
-  // are staged per round; 6 split products of 16 cycles replace 16 exact-f32 MFMAs of 32 cycles per pair of 16x16 blocks
-  static constexpr bool WG_BF16 = BF16 && (NB_ <= 2) && (NDQ_WG_BF16 != 0);
   // WG32 (wide nets, H = 64): the hidden-layer weight gradients on v_mfma_f32_32x32x16_bf16 -- K = 16 is exactly the 16
   // points of ONE stream, so no second stream has to be staged (there is no LDS left for it); per stream 4 macro-blocks
   // x 6 split products of 32 cycles (768) replace 64 exact-f32 MFMAs of 32 cycles (2 048); the accumulators are 32x32
   // blocks (GradAcc::w32: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5))
-  static constexpr bool WG32 = BF16 && (NB_ == 4) && (NDQ_WG32 != 0);
-  static constexpr int WG_SB = (NB_ <= 2 && SS::NS >= 2 && (BWD_THREADS == 256 || WG_BF16)) ? 2 : 1;
+  static constexpr bool WG32 = BF16 && (NB_ == 4);
+  static constexpr int WG_SB = (NB_ <= 2 && SS::NS >= 2 && BWD_THREADS == 256) ? 2 : 1;
   static constexpr int stageFloatsPlain = WG_SB * 2 * 16 * HP;    // Zt and Ht tiles of WG_SB streams
   // WG_TR (H = 32 on the bf16x3 path, closure kernels built with NDQ_WG_TR): dW_l += sum_s Zbar_s H_s^T contracts over
   // POINTS, which the fragment layout keeps in lanes -- both operands have to be transposed.  The exact-f32 route stages
@@ -774,7 +745,7 @@ struct Cfg {
   static constexpr int trHimg = (L_ - 1) * SS::NS * 3 * trPlane;
   static constexpr int trStage = trHimg + 2 * 3 * trPlane;
   static constexpr int trWaves = NDQ_WG_TR_K == 1 ? BWD_THREADS / 64 : (NDQ_WG_TR_K == 2 ? NDQ_MULTI_G2 : 1);   // per network
-  static constexpr bool WG_TR = BF16 && (NB_ == 2) && (L_ >= 2) && (NOUT_ == 1) && (NDQ_WG_TR != 0) && !WG_BF16 &&
+  static constexpr bool WG_TR = BF16 && (NB_ == 2) && (L_ >= 2) && (NOUT_ == 1) && (NDQ_WG_TR != 0) &&
                                 (NDQ_WG_TR_K * (ldsWeightsEnd(true) + trWaves * trStage) +
                                  (NDQ_WG_TR_K > 1 ? 2 * trWaves * NDQ_WG_TR_K * SS::NS * 16 : 0) + 64 <= 40 * 1024);
   // WG_TR64 (H = 64, same switch): the 32x32x16 weight-gradient GEMM of WG32 fed the same way.  There is no LDS to keep
@@ -796,8 +767,8 @@ struct Cfg {
   // no scratch.  (Keeping them in the source as well -- KeptPlanes for the last layer, a struct of factors handed to
   // act_backward -- compiles to the same instructions, so the source stays as it was.)
   static constexpr bool REUSE_FWD = (NB_ == 2) && (BWD_THREADS != 256) && WG_TR && (NDQ_WG_TR_K == 1) && (ACTP_ == 0) &&
-                                    (SS::NS <= 6) && (NDQ_F64 == 0) && (NDQ_REUSE_FWD != 0);
-  static constexpr bool LAUNDER = ((NB_ == 2) && (BWD_THREADS != 256) && !REUSE_FWD) || (NB_ >= 4 && NDQ_WIDE_LAUNDER);
+                                    (SS::NS <= 6) && (NDQ_F64 == 0);
+  static constexpr bool LAUNDER = ((NB_ == 2) && (BWD_THREADS != 256) && !REUSE_FWD) || (NB_ >= 4);
 };
 // Cfg with REUSE_FWD taken back (fused_closure_loop_kernel: its 8-wave build is over the register file as it is -- 256
 // registers, 216 B of scratch -- and everything the compiler keeps in addition is spilled)
@@ -843,6 +814,29 @@ __device__ __forceinline__ real actp_mul(real v, real f) {
   else return v;
 }
 
+// One weight W[j][k] (out j, in k) of a bf16x3 layer image: split once, scatter twice.  "bf16 fragment order": A operand of
+// (ob = 16-row output block, c = chunk of 32 contraction slots), plane pl: lane (i = lane&15, kg = lane>>4) holds 8 bf16,
+// slot e <-> unit 16*(2c + (e>>2)) + 4*kg + (e&3); index in bf16 units: ((((ob*NCF + c)*3 + pl)*64 + lane)*8 + e.
+// NCF / NCT: chunks per block row of the forward / of the transposed image (the contraction widths differ for the output layer)
+// Used by the two output-matrix sites of stage_weights.  Its two hidden-layer sites (place, the loop over l) keep the same
+// sequence written out: through this function the compiler schedules 76 (place) and 1 (loop) of libndq.so's kernels
+// differently -- same instruction counts and registers, other order.
+template <bool BWD, int NCF, int NCT>
+__device__ __forceinline__ void place_planes(__bf16* wf, __bf16* wt, int j, int k, real w) {
+  const __bf16 w0 = (__bf16)w; const real r1 = w - (real)w0;
+  const __bf16 w1 = (__bf16)r1; const __bf16 w2 = (__bf16)(r1 - (real)w1);
+  {  // forward image: block (ob = j/16, c = k/32), lane (j%16, kg = (k%16)/4), slot e = 4*((k%32)/16) + k%4
+    const int blk = (j >> 4) * NCF + (k >> 5);
+    const int base = ((blk * 3) * 64 + (j & 15) + 16 * ((k & 15) >> 2)) * 8 + 4 * ((k & 31) >> 4) + (k & 3);
+    wf[base] = w0; wf[base + 512] = w1; wf[base + 1024] = w2;
+  }
+  if (BWD) {  // transposed image: block (ob = k/16, c = j/32), lane (k%16, kg = (j%16)/4), slot e = 4*((j%32)/16) + j%4
+    const int blk = (k >> 4) * NCT + (j >> 5);
+    const int base = ((blk * 3) * 64 + (k & 15) + 16 * ((j & 15) >> 2)) * 8 + 4 * ((j & 31) >> 4) + (j & 3);
+    wt[base] = w0; wt[base + 512] = w1; wt[base + 1024] = w2;
+  }
+}
+
 // tid / nt: this thread's index among the nt threads that stage the image together (default: the whole workgroup; the
 // multi-network closure lets every network's own waves stage that network's image, all images at once)
 template <class C, bool BWD>
@@ -857,13 +851,13 @@ __device__ __forceinline__ void stage_weights(real* lds, const real* __restrict_
     else return actp_mul<C>(prm[idx], f);
   };
   auto real_unit = [](int j, int hw) { return !C::RAGGED || j < hw; };
-#if NDQ_STAGE_INFLIGHT
   // ---- plain FCNNs on the bf16x3 path (the BASELINE shapes): ONE pass over the flat parameter vector in torch order with the
   // loads of a pass all in flight (round 5).  The loops below stage array by array -- W1, b1, Wout, bout, W_l, b_l -- and every
   // loop compiles to "load, s_waitcnt vmcnt(0), ds_write, branch": five (C2) dependent round trips to memory that the previous
   // step's tail launch wrote on other XCDs, 1.35 us of every launch.  Here a thread loads its elements e = base + tid + k nt,
   // k < KP, unconditionally (clamped), one empty asm statement keeps all KP values live at once, and place() puts element e
-  // where the loops below would have put it (same LDS images, bit for bit).
+  // where the loops below would have put it (same LDS images, bit for bit).  Measured against array-by-array staging of these
+  // shapes: profiles/r05f_staging_ab.md.
   if constexpr (C::ACTP == 0 && !C::RAGGED && C::MONO == 0 && C::SKIP == 0 && C::BF16 && (C::NOUT == 1 || C::BF16O)) {
     constexpr int KP = 8, P = C::P, LS = H * H + H;          // LS: flat stride of one hidden layer (matrix + bias)
     // multi-output networks on the bf16 matrix core (BF16O): planes of the zero-padded output matrix Wo [HO][H], forward and
@@ -871,18 +865,7 @@ __device__ __forceinline__ void stage_weights(real* lds, const real* __restrict_
     auto place_wout = [&](int j, int k, real w) {
       __bf16* wf = reinterpret_cast<__bf16*>(lds + C::ldsWout(BWD));
       __bf16* wt = reinterpret_cast<__bf16*>(lds + C::ldsWoutT());
-      const __bf16 w0 = (__bf16)w; const real r1 = w - (real)w0;
-      const __bf16 w1 = (__bf16)r1; const __bf16 w2 = (__bf16)(r1 - (real)w1);
-      {
-        const int blk = (j >> 4) * C::NC + (k >> 5);
-        const int base = ((blk * 3) * 64 + (j & 15) + 16 * ((k & 15) >> 2)) * 8 + 4 * ((k & 31) >> 4) + (k & 3);
-        wf[base] = w0; wf[base + 512] = w1; wf[base + 1024] = w2;
-      }
-      if (BWD) {
-        const int blk = (k >> 4) * C::NCO + (j >> 5);
-        const int base = ((blk * 3) * 64 + (k & 15) + 16 * ((j & 15) >> 2)) * 8 + 4 * ((j & 31) >> 4) + (j & 3);
-        wt[base] = w0; wt[base + 512] = w1; wt[base + 1024] = w2;
-      }
+      place_planes<BWD, C::NC, C::NCO>(wf, wt, j, k, w);
     };
     if constexpr (C::NOUT > 1) {                             // padding rows NOUT .. HO - 1 of Wo and of bout: exact zeros
       for (int i = C::NOUT * H + tid; i < C::HO * H; i += nt) place_wout(i / H, i % H, (real)0.f);
@@ -935,7 +918,6 @@ __device__ __forceinline__ void stage_weights(real* lds, const real* __restrict_
     }
     return;
   }
-#endif
   for (int i = tid; i < C::NIN * H; i += nt) {  // W1T[a][j] = W1[j][a]  (MONO: a runs over the NIN features)
     const int a = i / H, j = i - a * H;
     lds[C::ldsW1T + i] = unit(j, C::hr(1), C::offW1 + j * C::NIN + a, f1);
@@ -968,18 +950,7 @@ __device__ __forceinline__ void stage_weights(real* lds, const real* __restrict_
       real w;
       if constexpr (C::RAGGED) w = (j < C::NOUT && k < HL) ? actp_mul<C>(Wo[j * HL + k], fo) : 0.f;
       else w = j < C::NOUT ? actp_mul<C>(Wo[i], fo) : 0.f;
-      const __bf16 w0 = (__bf16)w; const real r1 = w - (real)w0;
-      const __bf16 w1 = (__bf16)r1; const __bf16 w2 = (__bf16)(r1 - (real)w1);
-      {
-        const int blk = (j >> 4) * C::NC + (k >> 5);
-        const int base = ((blk * 3) * 64 + (j & 15) + 16 * ((k & 15) >> 2)) * 8 + 4 * ((k & 31) >> 4) + (k & 3);
-        wf[base] = w0; wf[base + 512] = w1; wf[base + 1024] = w2;
-      }
-      if (BWD) {
-        const int blk = (k >> 4) * C::NCO + (j >> 5);
-        const int base = ((blk * 3) * 64 + (k & 15) + 16 * ((j & 15) >> 2)) * 8 + 4 * ((j & 31) >> 4) + (j & 3);
-        wt[base] = w0; wt[base + 512] = w1; wt[base + 1024] = w2;
-      }
+      place_planes<BWD, C::NC, C::NCO>(wf, wt, j, k, w);
     }
     for (int i = tid; i < C::HO; i += nt) lds[C::ldsbout(BWD) + i] = i < C::NOUT ? prm[C::offbout + i] : 0.f;
   } else {
@@ -1003,28 +974,26 @@ __device__ __forceinline__ void stage_weights(real* lds, const real* __restrict_
     for (int i = tid; i < C::HO; i += nt) lds[C::ldsbout(BWD) + i] = i < C::NOUT ? prm[C::offbout + i] : 0.f;
   }
   if constexpr (C::BF16) {
-    // bf16x3 planes in "bf16 fragment order": A operand of (ob = 16-row output block, c = chunk of 32 contraction
-    // slots), plane pl: lane (i = lane&15, kg = lane>>4) holds 8 bf16, slot e <-> unit 16*(2c + (e>>2)) + 4*kg + (e&3).
-    // index in bf16 units: ((((ob*NC + c)*3 + pl)*64 + lane)*8 + e
+    // bf16x3 planes in "bf16 fragment order" (place_planes; written out here, see there)
 #pragma unroll
     for (int l = 2; l <= C::L; ++l) {
       const real* W = prm + C::offW(l);
       __bf16* wf = reinterpret_cast<__bf16*>(lds + C::ldsWf(l, BWD));
       __bf16* wt = reinterpret_cast<__bf16*>(lds + C::ldsWt(l));
       const real fb = act_pre<C>(prm, l), fw = actp_mul<C>(fb, act_post<C>(prm, l - 1));
-      for (int i = tid; i < H * H; i += nt) {   // one coalesced pass over W[j][k] (out j, in k): split once, scatter twice
+      for (int i = tid; i < H * H; i += nt) {   // one coalesced pass over W[j][k] (out j, in k)
         const int j = i / H, k = i - j * H;
         real w;
         if constexpr (C::RAGGED) w = (j < C::hr(l) && k < C::hr(l - 1)) ? actp_mul<C>(W[j * C::hr(l - 1) + k], fw) : 0.f;
         else w = actp_mul<C>(W[i], fw);
         const __bf16 w0 = (__bf16)w; const real r1 = w - (real)w0;
         const __bf16 w1 = (__bf16)r1; const __bf16 w2 = (__bf16)(r1 - (real)w1);
-        {  // forward image: block (ob = j/16, c = k/32), lane (j%16, kg = (k%16)/4), slot e = 4*((k%32)/16) + k%4
+        {
           const int blk = (j >> 4) * C::NC + (k >> 5);
           const int base = ((blk * 3) * 64 + (j & 15) + 16 * ((k & 15) >> 2)) * 8 + 4 * ((k & 31) >> 4) + (k & 3);
           wf[base] = w0; wf[base + 512] = w1; wf[base + 1024] = w2;
         }
-        if (BWD) {  // transposed image: block (ob = k/16, c = j/32), lane (k%16, kg = (j%16)/4), slot e = 4*((j%32)/16) + j%4
+        if (BWD) {
           const int blk = (k >> 4) * C::NC + (j >> 5);
           const int base = ((blk * 3) * 64 + (k & 15) + 16 * ((j & 15) >> 2)) * 8 + 4 * ((j & 31) >> 4) + (j & 3);
           wt[base] = w0; wt[base + 512] = w1; wt[base + 1024] = w2;
@@ -1061,7 +1030,7 @@ __device__ __forceinline__ real4 lds4(const real* p) { return *reinterpret_cast<
 template <class C>
 __device__ __forceinline__ int opaque_zero() {
   int z = 0;
-  if constexpr ((C::WIDE || C::BWD_THREADS != 256) && (NDQ_PIN_WEIGHT_READS != 0)) asm volatile("" : "+v"(z));
+  if constexpr (C::WIDE || C::BWD_THREADS != 256) asm volatile("" : "+v"(z));
   return z;
 }
 
@@ -1371,6 +1340,8 @@ template <class C> __device__ __forceinline__ void zero_frag(real4 (&z)[C::NS][C
 
 // split the 8 fp32 values a lane holds for one K-chunk (blocks 2c, 2c+1) into three bf16x8 operands
 // (NP = 2: the third plane is left unset -- for operands nobody reads it of, see NDQ_H_PLANES / NDQ_Z_PLANES above)
+// (measured against a body on 2-wide vectors -- v_cvt_pk_bf16_f32, packed subtractions: 3.5 % fewer VALU instructions in
+// C3's closure kernel, no time gained: C3 418.4 -> 419.8 us, C2 8-wave 19.9 -> 19.7 us on MI355X)
 template <int NP = 3>
 __device__ __forceinline__ void split3(const real4 a, const real4 b, bf16x8 (&pl)[3]) {
   const real x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
@@ -1379,23 +1350,6 @@ __device__ __forceinline__ void split3(const real4 a, const real4 b, bf16x8 (&pl
     for (int e = 0; e < 8; ++e) { pl[0][e] = (__bf16)x[e]; pl[1][e] = pl[0][e]; pl[2][e] = pl[0][e]; }
     return;
   }
-#if NDQ_SPLIT_PAIRS && !NDQ_F64
-  // two values at a time on 2-wide vector types: one v_cvt_pk_bf16_f32 per pair and plane, packed subtractions
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f32x2 v = {x[2 * k], x[2 * k + 1]};
-    const bf16x2 h0 = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(h0, f32x2);
-    const bf16x2 h1 = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(h1, f32x2);
-    const bf16x2 h2 = __builtin_convertvector(r2, bf16x2);
-    pl[0][2 * k] = h0[0]; pl[0][2 * k + 1] = h0[1];
-    pl[1][2 * k] = h1[0]; pl[1][2 * k + 1] = h1[1];
-    pl[2][2 * k] = h2[0]; pl[2][2 * k + 1] = h2[1];
-  }
-#else
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const __bf16 h0 = (__bf16)x[e];
@@ -1404,7 +1358,6 @@ __device__ __forceinline__ void split3(const real4 a, const real4 b, bf16x8 (&pl
     pl[0][e] = h0; pl[1][e] = h1;
     if constexpr (NP == 3) pl[2][e] = (__bf16)(r1 - (real)h1);
   }
-#endif
 }
 
 // NDQ_FWD_BF16X1: plane 0 alone (round to nearest even), the other two stay unset and unread
@@ -1647,11 +1600,12 @@ __device__ __forceinline__ void hidden_layer_planes(const real* lds, int l, int 
   }
 }
 
-// cross-lane sums: the 4 lane groups are combined through ds_bpermute (NDQ_QUAD_SWAP: v_permlane16/32_swap, an
-// experiment), the 16 points of a tile -- exactly one DPP row -- by DPP row rotations fused into the adds.  Every lane
-// ends up with the total.
+// cross-lane sums: the 4 lane groups are combined through v_permlane16/32_swap (fp64: ds_bpermute), the 16 points of a
+// tile -- exactly one DPP row -- by DPP row rotations fused into the adds.  Every lane ends up with the total.
+// (fp32, measured against the ds_bpermute route: same bits, C2 closure 17.52 -> 17.03 us, profiles/r06h_flags_ab_c2.txt,
+// r06j_own_tile_ab.txt)
 __device__ __forceinline__ real quad_sum(real v) {  // sum over the 4 lane groups q (lanes p, p+16, p+32, p+48)
-#if NDQ_QUAD_SWAP && !NDQ_F64
+#if !NDQ_F64
   // v_permlane16_swap / v_permlane32_swap exchange rows between TWO registers; swapping a value with a copy of itself
   // leaves (own row, partner row) in the pair, whose sum is what v + shfl_xor(v, 16 / 32) computes -- the same two
   // operands, so the same bits (scripts/ubench_permlane_swap.hip) -- on the VALU, without the LDS round trip
@@ -2108,44 +2062,6 @@ __device__ __forceinline__ void weight_grad(real* stage, int lane, int p, int q,
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       return;
     }
-    if constexpr (C::WG_BF16) {
-      // contraction slot 8 kg + e of the 32-wide bf16 MFMA <-> stream s0 + (kg >> 1), point (e & 3) + 8 (e >> 2) + 4 (kg & 1)
-      // (the same map on both operands; this point order keeps the b32 reads of the two lane groups of a half-wave
-      // 16 banks apart: 4 HP = 16 mod 32).  A lane therefore reads 8 points of ONE unit of ONE stream per block,
-      // splits them into three bf16 planes, and the six significant plane products go through the matrix core.
-      const int kg = lane >> 4;
-      const bool live = sn == 2 || (kg >> 1) < sn; // a round with one stream: the upper half of the slots is zero
-      const real* Zt = stage + (live ? (kg >> 1) : 0) * 2 * 16 * HP + (4 * (kg & 1)) * HP + (lane & 15);
-      const real* Ht = Zt + 16 * HP;
-      auto planes_of = [&](const real* t, int b, bf16x8 (&pl)[3]) {
-        real x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const real v = t[((e & 3) + 8 * (e >> 2)) * HP + 16 * b];
-          if constexpr (sn == 2) x[e] = v;
-          else x[e] = live ? v : 0.f;
-        }
-        split3<NDQ_HTR_PLANES>(real4{x[0], x[1], x[2], x[3]}, real4{x[4], x[5], x[6], x[7]}, pl);
-      };
-      bf16x8 pb[C::NB][3];
-#pragma unroll
-      for (int b = 0; b < C::NB; ++b) planes_of(Ht, b, pb[b]);
-#pragma unroll
-      for (int jb = 0; jb < NBA; ++jb) {
-        bf16x8 pa[3];
-        planes_of(Zt, jb, pa);
-#pragma unroll
-        for (int kb = 0; kb < C::NB; ++kb) {
-#define NDQ_W(I, J) acc[jb][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[I], pb[kb][J], acc[jb][kb], 0, 0, 0);
-          NDQ_WPRODUCTS(NDQ_W)
-#undef NDQ_W
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      return;
-    }
     // all operands of the round are read into registers of their own BEFORE the first MFMA: one LDS round trip per
     // round instead of one per k-step (the compiler otherwise recycles four registers and waits 16 times per stream)
     if constexpr (C::BWD_THREADS != 256) {
@@ -2185,9 +2101,7 @@ __device__ __forceinline__ void weight_grad(real* stage, int lane, int p, int q,
         for (int b = 0; b < C::NB; ++b) bv[k][st][b] = Ht[(4 * q + st) * HP + 16 * b + p];
       }
     });
-#if NDQ_WG_SCHED_BARRIER
     __builtin_amdgcn_sched_barrier(0);          // keep the reads above the MFMAs
-#endif
     sfor<sn>([&](auto k_) {
       constexpr int k = decltype(k_)::value;
 #pragma unroll
@@ -3238,12 +3152,6 @@ __device__ __forceinline__ void fused_closure_body(const FusedArgs& a, real* lds
   real xe[NXE > 0 ? NXE : 1], tsum[PW::NT > 0 ? PW::NT : 1];
 #pragma unroll
   for (int j = 0; j < PW::NT; ++j) { xe[PW::ND + j] = a.theta[j]; tsum[j] = 0.f; }
-#if NDQ_STAGGER > 0
-  // two waves per SIMD run the same phases (VALU-heavy activation math, MFMA-heavy GEMMs) in lockstep and then compete for
-  // the same pipe; delaying the second wave of every SIMD by a fraction of a tile lets one's MFMAs run under the
-  // other's VALU work
-  if (WAVES > 4 && wave >= WAVES / 2) __builtin_amdgcn_s_sleep(NDQ_STAGGER);
-#endif
   for (int tile = blk * WAVES + wave; tile < ntiles; tile += nblk * WAVES) {
     const int n = tile * 16 + p;
     const bool valid = n < a.n;
@@ -3783,7 +3691,7 @@ __device__ __forceinline__ void fused_group_closure_body(const FusedArgs& a, rea
   constexpr int G = group_tiles<C>(), GP = 16 * G;      // tiles / points per group
   const int ngroups = (a.n + GP - 1) / GP;
   // the first group's coordinates are requested before the weights are staged, every later group's one group ahead (round 5:
-  // the load sat at the top of the group loop, its HBM latency exposed once per group -- the tile kernels always prefetched)
+  // the load sat at the top of the group loop, its HBM latency exposed once per group -- the tile kernels always prefetched; measured against that, profiles/r05h_c4_ab.jsonl)
   real cn[PW::NC];
   {
     const int n0 = (blk * WAVES + wave) * GP + lane;
@@ -3814,14 +3722,6 @@ __device__ __forceinline__ void fused_group_closure_body(const FusedArgs& a, rea
 #pragma unroll
       for (int d = 0; d < PW::NC; ++d) cn[d] = a.coords[(size_t)d * a.ldc + nn1];
     }
-#if !NDQ_GROUP_PREFETCH      // (A/B: the load at the top of the group loop, as in rounds 2 - 4)
-    {
-      const int nn = valid ? n : a.n - 1;
-#pragma unroll
-      for (int d = 0; d < PW::NC; ++d) c[d] = a.coords[(size_t)d * a.ldc + nn];
-      asm volatile("" : "+v"(c[0]));
-    }
-#endif
     // ---- phase 1: forward streams of the 4 tiles -> X
     NDQ_TT(0);
     NDQ_UNROLL(NDQ_GROUP_U1)

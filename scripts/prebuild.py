@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Pre-compile (hipcc, no GPU needed) the generated kernels of some test configs under the CURRENT environment -- e.g. with
-NDQ_JIT_FLAGS="-DNDQ_DEEP_XCD_REMAP=0" for an A/B run -- so that the GPU box finds them in neurodiffeq_amd/_jit instead of
+NDQ_JIT_FLAGS="-DNDQ_DEEP_WGBF_PF=4" for an A/B run -- so that the GPU box finds them in neurodiffeq_amd/_jit instead of
 compiling them inside a timed gpurun call.   usage: [NDQ_JIT_FLAGS=...] scripts/prebuild.py w18 w19:256 ...
 Not part of build(): __graft_entry__.build() prunes modules it did not build itself, so run this AFTER build() (or with
 NDQ_BUILD_NO_PRUNE=1 set for the next build())."""
